@@ -1,8 +1,17 @@
 """bench.py -- full RMT time step (soft disc in the lid-driven cavity, configs 2/4
 physics) on MI355X: cell-updates/s at N=4096 (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--n 4096] [--no-cpu-baseline]
-                  [--config 4|2|3|5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--n 4096] [--config 4|2|3|5]
+                  [--dump-outputs DIR] [--full [--no-cpu-baseline] [--cpu-steps C]]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line with the headline
+figure (`value`, `ms_per_step`).  --dump-outputs DIR then writes what the last timed step left
+(the state planes and the per-step diagnostics) as DIR/<name>.npy in float64; a plane larger
+than its share of the 48 MB budget is written as a fixed, seeded sample of its cells, so two
+builds run with the same arguments can be compared output for output.  --full adds everything
+else: a second, profiled, pass of the same K steps (phase breakdown, the k_mom_stage roofline),
+the step / compute / latency rooflines from the committed counter passes, and the CPU
+baselines of the oracle (--no-cpu-baseline leaves those out of a --full run).
 
 --config names a BASELINE.json configuration (default 4, the one the metric is quoted on):
   2  soft_disc_in_lid_driven N=256 semilagrangian        (208 B/cell)
@@ -106,6 +115,31 @@ def _dist():
     return ws, rank, local
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # of float64, all files of one --dump-outputs together
+DUMP_SEED = 4096
+
+
+class _Dump:
+    """--dump-outputs: DIR/<name>.npy in float64.  An array with more elements than its share
+    of the budget is written as its values at a fixed set of flat indices (drawn once per
+    array size from DUMP_SEED, sorted), the same in every run."""
+
+    def __init__(self, dirname, n_arrays):
+        self.dir = dirname
+        self.cap = DUMP_BUDGET_BYTES // 8 // max(1, n_arrays)
+        self._idx = {}
+        os.makedirs(dirname, exist_ok=True)
+
+    def add(self, name, a):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size > self.cap:
+            if a.size not in self._idx:
+                rng = np.random.default_rng(DUMP_SEED)
+                self._idx[a.size] = np.sort(rng.choice(a.size, self.cap, replace=False))
+            a = a.reshape(-1)[self._idx[a.size]]
+        np.save(os.path.join(self.dir, name + ".npy"), a)
+
+
 def cpu_baseline(n, steps):
     """The oracle (C restatement of the reference's Numba kernels + the same NumPy/SciPy
     calls) timed on this host, two ways: faithful threading (OpenMP only in the kernels the
@@ -190,6 +224,18 @@ def main_config(args, cfg):
     el = time.perf_counter() - t0
     d = sim.diagnostics()
     assert np.all(np.isfinite(np.asarray(d["cx"]))), "non-finite state"
+    if args.dump_outputs:
+        discs = range(len(sim.specs)) if cfg == 5 else (0,)
+        planes = [("u", 0), ("v", 0), ("p", 0)] + [(f, k) for k in discs
+                                                   for f in ("X1", "X2", "phi")]
+        dump = _Dump(args.dump_outputs, len(planes))
+        for f, k in planes:
+            if cfg == 5:
+                dump.add(f if f in ("u", "v", "p") else f"{f}_disc{k}", sim.get(f, k))
+            else:
+                dump.add(f, sim.get(f))
+        for k, v in d.items():
+            dump.add("diag_" + k, v)
     value = N * N * args.steps / el
     gbs = value * alg / 1e9
     out = {"metric": f"cell-updates/s (full RMT step) at N={N}; achieved HBM GB/s vs peak",
@@ -212,9 +258,56 @@ def main_config(args, cfg):
         out["roofline"].update({"traffic": per_step, "traffic_unit": "bytes per step",
                                 "traffic_rev": tj.get("git_rev"),
                                 "measured_GBs": per_step / (el / args.steps) / 1e9})
-    if not args.no_cpu_baseline and cfg in (3, 5):
+    if args.full and not args.no_cpu_baseline and cfg in (3, 5):
         out["cpu_baseline"] = cpu_baseline_cfg(cfg, N)
     print(json.dumps(out), flush=True)
+
+
+def _full_figures(args, sim, md, ws, N, value, elapsed, elapsed_prof, ph):
+    """--full, config 4: the keys beside the headline figure (kernel, compute, latency and step
+    rooflines, the phase breakdown of the profiled pass, the CPU baselines)."""
+    traffic, step_traffic, pmc_rev = _pmc(N, 2 if md else 1)
+    rk_ms, rk_intervals = ph["rk4_stage_kernels"]
+    rk_launches = rk_intervals if not md else 4 * rk_intervals
+    per_launch_s = rk_ms / 1e3 / rk_launches
+    # achieved: SURVEY 8(d)'s algorithmic bytes of the stress + RK4 pass (7 planes per cell
+    # for the 4 stage launches) spread over the launches, / the HIP-event launch time;
+    # a slab's cell-updates are its owned rows (the recomputed halo rows are overhead)
+    own = N * N if not md else (sim.slabs[0].r1 - sim.slabs[0].r0) * N
+    alg_per_launch = RK4_ALG_BYTES_PER_CELL * own / 4
+    achieved = alg_per_launch / per_launch_s / 1e9
+    ex_ms, ex_calls = ph["extrap_sweep_kernel" if not md else "extrap_chain_kernel"]
+    out = {
+        # the dominant HBM-bound kernel: the fused RK4 stage (4 launches per step)
+        "roofline": {"bound": "hbm", "kernel": "k_mom_stage (fused RK4 stage, 4 launches/step)",
+                     "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBS,
+                     "traffic": traffic, "traffic_rev": pmc_rev,
+                     "launch_ms": per_launch_s * 1e3,
+                     "alg_bytes_per_launch": alg_per_launch},
+        # ... whose own bound is the fp64 VALU issue rate (SQ counters; DESIGN.md section 4)
+        "compute_roofline": _f64_roof(N, 2 if md else 1, per_launch_s),
+        # the dominant kernel by time is not HBM-bound: the exact raster-order extrapolation
+        # chain (DESIGN.md section 5) runs on one workgroup, bounded by its dependency depth
+        "latency_bound": {"kernel": "k_ex_chain (exact serial-order extrapolation chain)",
+                          "ms_per_step": ex_ms / max(1, ex_calls),
+                          "dag_depth_fits": _chain_depth(N),
+                          "us_per_link": (ex_ms / max(1, ex_calls) * 1e3 / _chain_depth(N)
+                                          if _chain_depth(N) else None),
+                          "dag_source": "profiles/r05/chain_dag_n4096.json"},
+        "step_roofline": {"alg_bytes_per_cell": STEP_ALG_BYTES_PER_CELL,
+                          "per_gpu": True,
+                          "achieved_GBs": value / ws * STEP_ALG_BYTES_PER_CELL / 1e9,
+                          "frac": value / ws * STEP_ALG_BYTES_PER_CELL / 1e9 / HBM_PEAK_GBS,
+                          "traffic_per_step": step_traffic,
+                          "measured_GBs": (step_traffic / (elapsed / args.steps) / 1e9
+                                           if step_traffic else None)},
+        "ms_per_step_profiled": elapsed_prof / args.steps * 1e3,
+        "phase_ms_per_step": {k: v[0] / max(1, args.steps) for k, v in ph.items()},
+    }
+    if not args.no_cpu_baseline and ws == 1:
+        out["cpu_baseline"] = cpu_baseline(N, args.cpu_steps)
+    return out
 
 
 def main():
@@ -225,7 +318,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--grid", "--n", dest="n", type=int, default=4096)
     ap.add_argument("--cpu-steps", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baselines out")
+    ap.add_argument("--full", action="store_true",
+                    help="also the profiled pass, the rooflines and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step left as DIR/<name>.npy")
     args = ap.parse_args()
     if args.config != 4:
         if args.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
@@ -276,31 +374,36 @@ def main():
             el = float(t.item())
         return el
 
-    # `value`: the K steps with no profiling events; then the same K steps again with HIP
-    # events around each phase and around the dominant kernel's launches (the roofline and
-    # the phase breakdown come from this second timed region)
+    # `value`: the K steps with no profiling events
     elapsed = timed(args.steps)
-    sim.set_profiling(True)
-    elapsed_prof = timed(args.steps)
-    ph = sim.phase_times()
-    sim.set_profiling(False)
     d = sim.diagnostics()
     assert np.all(np.isfinite(d["cx"])) and np.all(np.isfinite(d["umax"])), "non-finite state"
+    if args.dump_outputs:
+        # every rank takes part in the gathers; rank 0 writes
+        planes = ("u", "v", "p", "X1", "X2") if md else ("u", "v", "p", "X1", "X2", "phi")
+        dump = _Dump(args.dump_outputs, len(planes)) if rank == 0 else None
+        for f in planes:
+            a = sim.gather(f) if md else sim.get(f)
+            if rank == 0:
+                dump.add(f, a)
+        if rank == 0:
+            for k, v in d.items():
+                dump.add("diag_" + k, v)
+
+    if args.full:
+        # the same K steps again with HIP events around each phase and around the dominant
+        # kernel's launches (the roofline and the phase breakdown come from this second timed
+        # region)
+        sim.set_profiling(True)
+        elapsed_prof = timed(args.steps)
+        ph = sim.phase_times()
+        sim.set_profiling(False)
+        d = sim.diagnostics()
+        assert np.all(np.isfinite(d["cx"])) and np.all(np.isfinite(d["umax"])), "non-finite state"
 
     if rank == 0:
         cells = N * N * args.steps          # one problem (strong scaling when ws > 1)
         value = cells / elapsed
-        traffic, step_traffic, pmc_rev = _pmc(N, 2 if md else 1)
-        rk_ms, rk_intervals = ph["rk4_stage_kernels"]
-        rk_launches = rk_intervals if not md else 4 * rk_intervals
-        per_launch_s = rk_ms / 1e3 / rk_launches
-        # achieved: SURVEY 8(d)'s algorithmic bytes of the stress + RK4 pass (7 planes per cell
-        # for the 4 stage launches) spread over the launches, / the HIP-event launch time;
-        # a slab's cell-updates are its owned rows (the recomputed halo rows are overhead)
-        own = N * N if not md else (sim.slabs[0].r1 - sim.slabs[0].r0) * N
-        alg_per_launch = RK4_ALG_BYTES_PER_CELL * own / 4
-        achieved = alg_per_launch / per_launch_s / 1e9
-        ex_ms, ex_calls = ph["extrap_sweep_kernel" if not md else "extrap_chain_kernel"]
         out = {
             "metric": "cell-updates/s (full RMT step) at N=4096; achieved HBM GB/s vs peak",
             "value": value, "unit": "cell-updates/s", "n_gpus": ws, "steps": args.steps,
@@ -312,35 +415,9 @@ def main():
                                    "(configs 2/4 loop body)", "grid": N,
                        "parallelism": (f"slab{ws} (row slabs, {'RCCL' if backend == 'nccl' else backend})"
                                        if md else "single-gpu")},
-            # the dominant HBM-bound kernel: the fused RK4 stage (4 launches per step)
-            "roofline": {"bound": "hbm", "kernel": "k_mom_stage (fused RK4 stage, 4 launches/step)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_rev": pmc_rev,
-                         "launch_ms": per_launch_s * 1e3,
-                         "alg_bytes_per_launch": alg_per_launch},
-            # ... whose own bound is the fp64 VALU issue rate (SQ counters)
-            "compute_roofline": _f64_roof(N, 2 if md else 1, per_launch_s),
-            # the dominant kernel by time is not HBM-bound: the exact raster-order extrapolation
-            # chain runs on one workgroup, bounded by its dependency depth
-            "latency_bound": {"kernel": "k_ex_chain (exact serial-order extrapolation chain)",
-                              "ms_per_step": ex_ms / max(1, ex_calls),
-                              "dag_depth_fits": _chain_depth(N),
-                              "us_per_link": (ex_ms / max(1, ex_calls) * 1e3 / _chain_depth(N)
-                                              if _chain_depth(N) else None),
-                              "dag_source": "profiles/r05/chain_dag_n4096.json"},
-            "step_roofline": {"alg_bytes_per_cell": STEP_ALG_BYTES_PER_CELL,
-                              "per_gpu": True,
-                              "achieved_GBs": value / ws * STEP_ALG_BYTES_PER_CELL / 1e9,
-                              "frac": value / ws * STEP_ALG_BYTES_PER_CELL / 1e9 / HBM_PEAK_GBS,
-                              "traffic_per_step": step_traffic,
-                              "measured_GBs": (step_traffic / (elapsed / args.steps) / 1e9
-                                               if step_traffic else None)},
-            "ms_per_step_profiled": elapsed_prof / args.steps * 1e3,
-            "phase_ms_per_step": {k: v[0] / max(1, args.steps) for k, v in ph.items()},
         }
-        if not args.no_cpu_baseline and ws == 1:
-            out["cpu_baseline"] = cpu_baseline(N, args.cpu_steps)
+        if args.full:
+            out.update(_full_figures(args, sim, md, ws, N, value, elapsed, elapsed_prof, ph))
         print(json.dumps(out), flush=True)
     if md:
         dist.destroy_process_group()

@@ -30,9 +30,9 @@ for s in "$@"; do
         configs) timeout -k 10 900 $PYT tests/test_gpu_configs.py -s > "$O/configs.log" 2>&1 \
                    || { tail -40 "$O/configs.log"; exit 1; }
                grep -E "^\[|energy|passed|failed" "$O/configs.log" ;;
-        bench) timeout -k 10 600 python -u bench.py > "$O/bench.log" 2>&1 || { tail -20 "$O/bench.log"; exit 1; }
+        bench) timeout -k 10 600 python -u bench.py --full > "$O/bench.log" 2>&1 || { tail -20 "$O/bench.log"; exit 1; }
                tail -1 "$O/bench.log" | cut -c1-400 ;;
-        benchq) timeout -k 10 300 python -u bench.py --no-cpu-baseline > "$O/benchq.log" 2>&1 \
+        benchq) timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > "$O/benchq.log" 2>&1 \
                    || { tail -20 "$O/benchq.log"; exit 1; }
                tail -1 "$O/benchq.log" | cut -c1-400 ;;
         kt) timeout -k 10 400 rocprofv3 --kernel-trace --stats -T -f csv -d "$O/kt" -o bench -- \

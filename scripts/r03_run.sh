@@ -33,7 +33,7 @@ for s in "$@"; do
         smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 \
                    || { tail -20 "$O/smoke.log"; exit 1; }
                tail -1 "$O/smoke.log" ;;
-        benchfull) timeout -k 10 900 python -u bench.py > "$O/benchfull.log" 2>&1 \
+        benchfull) timeout -k 10 900 python -u bench.py --full > "$O/benchfull.log" 2>&1 \
                    || { tail -20 "$O/benchfull.log"; exit 1; }
                tail -1 "$O/benchfull.log" | cut -c1-300 ;;
         bench100) for k in 1 2 3; do
@@ -90,7 +90,7 @@ for s in "$@"; do
             python3 tools/chain_trace.py "$O/trace16.bin" > "$O/trace16.txt" && head -5 "$O/trace16.txt" ;;
         cfg:*)   # one BASELINE config's bench line (CPU baseline included) and its kernel stats
             c=${s#cfg:}
-            timeout -k 10 600 python -u bench.py --config $c --steps 10 --warmup 2 > "$O/cfg$c.log" 2>&1 \
+            timeout -k 10 600 python -u bench.py --full --config $c --steps 10 --warmup 2 > "$O/cfg$c.log" 2>&1 \
                 || { tail -20 "$O/cfg$c.log"; exit 1; }
             tail -1 "$O/cfg$c.log" | cut -c1-500
             timeout -k 10 300 rocprofv3 --kernel-trace --stats -T -f csv -d "$O/kt_cfg$c" -o bench -- \
