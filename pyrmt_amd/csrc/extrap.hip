@@ -804,7 +804,7 @@ size_t extrap_workspace(int ny, int nx, int max_layers, bool px) {
 // map is copied / read here and the call is simply the first half of extrapolate().
 int extrap_geometry(rmt_ctx *ctx, const double *X1, const double *X2, const double *phi,
                     double dx, double dy, int max_layers, double *X1o, double *X2o,
-                    const u64 *kin) {
+                    const u64 *kin, const ExtrapCall &call) {
     const int ny = ctx->ny, nx = ctx->nx;
     const int W = (nx + 63) / 64;
     RMT_CHECK(max_layers > 0 && ny >= 3 && nx >= 3 && ny < (1 << 20) && nx < (1 << 30),
@@ -840,32 +840,32 @@ int extrap_geometry(rmt_ctx *ctx, const double *X1, const double *X2, const doub
         // 64 workgroups: the disc's first rim rows end the search (this runs beside the
         // critical path when sim.hip prepares the next step's geometry early)
         int jb = 0, je = ny;
-        if (ctx->ex_none_rows[1] > ctx->ex_none_rows[0]) {
-            jb = std::max(0, ctx->ex_none_rows[0]);
-            je = std::min(ny, ctx->ex_none_rows[1]);
+        if (call.none_rows[1] > call.none_rows[0]) {
+            jb = std::max(0, call.none_rows[0]);
+            je = std::min(ny, call.none_rows[1]);
         }
-        if (ctx->ex_none_wide && ctx->ex_cand && je > jb) {
-            int *cnt = ctx->ex_cand + ctx->ex_cand_cap;
+        if (call.none_wide && call.cand && je > jb) {
+            int *cnt = call.cand + call.cand_cap;
             RMT_HIP(hipMemsetAsync(cnt, 0, sizeof(int), ctx->stream));
             int wb = 0, we = W;
-            if (ctx->ex_none_cols[1] > ctx->ex_none_cols[0]) {
-                wb = std::max(0, ctx->ex_none_cols[0]);
-                we = std::min(W, ctx->ex_none_cols[1]);
+            if (call.none_cols[1] > call.none_cols[0]) {
+                wb = std::max(0, call.none_cols[0]);
+                we = std::min(W, call.none_cols[1]);
             }
             k_ex_cand<<<grid1d((long)(je - jb) * (we - wb), 256), 256, 0, ctx->stream>>>(
-                ws.kbits, ny, nx, W, jb, je, wb, we, ctx->ex_cand, ctx->ex_cand_cap, cnt);
+                ws.kbits, ny, nx, W, jb, je, wb, we, call.cand, call.cand_cap, cnt);
             k_ex_none_list<<<1024, 256, 0, ctx->stream>>>(ws.kbits, ny, nx, W, dx, dy, r * r,
-                                                           ws.ctl, jb, je, ctx->ex_cand,
-                                                           ctx->ex_cand_cap, cnt);
+                                                           ws.ctl, jb, je, call.cand,
+                                                           call.cand_cap, cnt);
         } else {
-            k_ex_none<<<ctx->ex_none_wide ? grid1d(std::max(je - jb, 1), 4)
+            k_ex_none<<<call.none_wide ? grid1d(std::max(je - jb, 1), 4)
                                           : std::min<unsigned>(grid1d(ny, 4), 64),
                         256, 0, ctx->stream>>>(
                 ws.kbits, ny, nx, W, dx, dy, r * r, ws.ctl, jb, je);
         }
         k_ex_none_fin<<<1, 1, 0, ctx->stream>>>(ws.ctl);
         RMT_LAUNCHED();
-        if (ctx->ex_none_host && force == 0) {
+        if (call.none_host && force == 0) {
             // the verdict on the host: with no acceptable target every later pass of the call
             // exits at once on the device, so none is launched (extrap_finish: the status words
             // the identity leaves, both zero)
@@ -892,7 +892,7 @@ int extrap_geometry(rmt_ctx *ctx, const double *X1, const double *X2, const doub
 // The value half after extrap_geometry (same ctx, same map, same layers): the static terms of
 // the records, the fallback sweep (an early exit unless a capacity limit tripped), the chain.
 int extrap_finish(rmt_ctx *ctx, double dx, double dy, int max_layers, double *X1o, double *X2o,
-                  int *dev_status) {
+                  int *dev_status, const ExtrapCall &call) {
     const int ny = ctx->ny, nx = ctx->nx;
     const int W = (nx + 63) / 64;
     const bool par = ctx->ex_par;
@@ -902,17 +902,17 @@ int extrap_finish(rmt_ctx *ctx, double dx, double dy, int max_layers, double *X1
     if (ctx->ex_noop_skip) {   // (extrap_geometry: nothing to fit, the map is left as it is)
         ctx->ex_noop_skip = false;
         if (dev_status) RMT_HIP(hipMemsetAsync(dev_status, 0, 2 * sizeof(int), ctx->stream));
-        if (ctx->ev_chain) RMT_HIP(hipEventRecord(ctx->ev_chain, ctx->stream));
+        if (call.chain_event) RMT_HIP(hipEventRecord(call.chain_event, ctx->stream));
         return RMT_OK;
     }
     const bool chain = ctx->ex_chain && !par;
     const int *ctl = ctx->ex_chain ? ws.ctl : nullptr;
-    if (chain) RMT_TRY(extrap_chain_values(ctx, ws, X1o, X2o, dx, dy, max_layers));
+    if (chain) RMT_TRY(extrap_chain_values(ctx, ws, X1o, X2o, dx, dy, max_layers, call));
     if (ctx->prof && !chain && !par) RMT_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
     ExSweep A{X1o, X2o, ws.kbits, ws.cbits, ws.Kold, ws.rowcand, ws.jrange, ny, nx, W,
               max_layers, dx, dy, ws.status, ctl};
     const bool prof = ctx->opt.ex_profile != 0;
-    const bool defer = chain && ctx->ex_sweep_defer && ctx->ev_chain;
+    const bool defer = chain && call.sweep_deferred && call.chain_event;
     RMT_CHECK(!defer || !dev_status, RMT_EINVAL,
               "extrap_finish: a deferred sweep leaves the status to the caller");
     if (defer) {
@@ -946,12 +946,12 @@ int extrap_finish(rmt_ctx *ctx, double dx, double dy, int max_layers, double *X1
     }
     if (ctx->prof && !chain && !par) RMT_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
     // the chain after the sweep: both read the fallback flag the chain prep settled
-    if (chain) RMT_TRY(extrap_chain_run(ctx, ws, X1o, X2o, max_layers));
+    if (chain) RMT_TRY(extrap_chain_run(ctx, ws, X1o, X2o, max_layers, call));
     if (par) {
         if (ctx->prof) RMT_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
         // the caller's work beside the extrapolation may start now (its combine pass is one
         // workgroup, as the chain)
-        if (ctx->ev_chain) RMT_HIP(hipEventRecord(ctx->ev_chain, ctx->stream));
+        if (call.chain_event) RMT_HIP(hipEventRecord(call.chain_event, ctx->stream));
         RMT_TRY(extrap_par_values(ctx, ws, X1o, X2o, max_layers));
         if (ctx->prof) RMT_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
     }
@@ -964,7 +964,8 @@ int extrap_finish(rmt_ctx *ctx, double dx, double dy, int max_layers, double *X1
     if (dev_status)
         RMT_HIP(hipMemcpyAsync(dev_status, ws.status, 2 * sizeof(int), hipMemcpyDeviceToDevice,
                                ctx->stream));
-    if (ctx->ev_chain && !chain && !par) RMT_HIP(hipEventRecord(ctx->ev_chain, ctx->stream));
+    if (call.chain_event && !chain && !par)
+        RMT_HIP(hipEventRecord(call.chain_event, ctx->stream));
     return RMT_OK;
 }
 
@@ -989,7 +990,7 @@ const int *extrap_status(rmt_ctx *ctx, int max_layers) {
 
 int extrapolate(rmt_ctx *ctx, const double *X1, const double *X2, const double *phi, double dx,
                 double dy, int max_layers, double *X1o, double *X2o, int *dev_status,
-                const u64 *kin) {
+                const u64 *kin, const ExtrapCall &call) {
     const long n = (long)ctx->ny * ctx->nx;
     if (max_layers <= 0) {
         if (X1o != X1) RMT_HIP(hipMemcpyAsync(X1o, X1, n * 8, hipMemcpyDeviceToDevice, ctx->stream));
@@ -997,8 +998,8 @@ int extrapolate(rmt_ctx *ctx, const double *X1, const double *X2, const double *
         if (dev_status) RMT_HIP(hipMemsetAsync(dev_status, 0, 2 * sizeof(int), ctx->stream));
         return RMT_OK;
     }
-    RMT_TRY(extrap_geometry(ctx, X1, X2, phi, dx, dy, max_layers, X1o, X2o, kin));
-    return extrap_finish(ctx, dx, dy, max_layers, X1o, X2o, dev_status);
+    RMT_TRY(extrap_geometry(ctx, X1, X2, phi, dx, dy, max_layers, X1o, X2o, kin, call));
+    return extrap_finish(ctx, dx, dy, max_layers, X1o, X2o, dev_status, call);
 }
 
 }  // namespace rmt

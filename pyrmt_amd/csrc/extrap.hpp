@@ -107,8 +107,9 @@ ExWs extrap_layout(void *base, int ny, int nx, int max_layers, size_t *bytes, bo
 int extrap_chain_prep(rmt_ctx *ctx, const ExWs &ws, const double *X1o, const double *X2o,
                       double dx, double dy, int ML);
 int extrap_chain_values(rmt_ctx *ctx, const ExWs &ws, const double *X1o, const double *X2o,
-                        double dx, double dy, int ML);
-int extrap_chain_run(rmt_ctx *ctx, const ExWs &ws, const double *X1o, const double *X2o, int ML);
+                        double dx, double dy, int ML, const ExtrapCall &call = {});
+int extrap_chain_run(rmt_ctx *ctx, const ExWs &ws, const double *X1o, const double *X2o, int ML,
+                     const ExtrapCall &call = {});
 bool extrap_chain_supported(int ny, int nx, int ML);
 // chain prep without the chain-order passes and with no records (the parallel mode only
 // needs targets and acceptance)

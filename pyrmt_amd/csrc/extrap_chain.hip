@@ -1239,23 +1239,24 @@ int extrap_chain_prep_px(rmt_ctx *ctx, const ExWs &ws, double dx, double dy, int
 
 // the value half of the records (after the map is advected; k_ex_vals)
 int extrap_chain_values(rmt_ctx *ctx, const ExWs &ws, const double *X1o, const double *X2o,
-                        double dx, double dy, int ML) {
+                        double dx, double dy, int ML, const ExtrapCall &call) {
     const int ny = ctx->ny, nx = ctx->nx, W = (nx + 63) / 64;
     const double r = 4 * std::sqrt(dx * dx + dy * dy);
     ExGeoArgs A{ws, X1o, X2o, ny, nx, W, 0, dx, dy, r * r, 0};
     const unsigned gblocks = (unsigned)std::min<long>(4096, std::max<long>(1, ws.maxt / 4));
     RMT_HIP(launch_done(ctx, k_ex_vals, dim3(gblocks), dim3(256), 0, ctx->stream,
-                        ctx->ev_chain_vals ? ctx->ev_chain : nullptr, A, ML));
+                        call.event_with_values ? call.chain_event : nullptr, A, ML));
     return RMT_OK;
 }
 
 int extrap_chain_run(rmt_ctx *ctx, const ExWs &ws, const double *X1o, const double *X2o,
-                     int ML) {
+                     int ML, const ExtrapCall &call) {
     hipStream_t st = ctx->stream;
     int ncol, nlg;
     const int nparts = chain_parts(ctx, ML, &ncol, &nlg);
     if (ctx->prof) RMT_HIP(hipEventRecord(ctx->ev[2], st));
-    if (ctx->ev_chain && !ctx->ev_chain_vals) RMT_HIP(hipEventRecord(ctx->ev_chain, st));
+    if (call.chain_event && !call.event_with_values)
+        RMT_HIP(hipEventRecord(call.chain_event, st));
     ChainArgs C{ws, (double *)X1o, (double *)X2o, ML, ws.status, nullptr};
     if (!ctx->opt.ex_profile) {
         k_ex_chain<false><<<nparts, CH_W * 64, 0, st>>>(C, nullptr);

@@ -948,27 +948,22 @@ int rmt_mac_sim_step(rmt_mac_sim *S, int nsteps, double t_end) {
                                 S->out + 8, S->kbits, box_mode ? cb : nullptr, face_sl));
             // the known plane from the advection pass (its k_ex_bits pass over phi_pre saved);
             // the no-op test over every row at once (a disc with nothing to fit scans them all)
-            ctx->ex_none_wide = true;
+            ExtrapCall ec;
+            ec.none_wide = true;
             // box mode: the known cells lie in rows [cb0, cb1) (kbits cleared elsewhere), so a
             // candidate -- an unknown 8-neighbour of a known cell -- in [cb0 - 1, cb1 + 1)
             if (box_mode) {
-                ctx->ex_none_rows[0] = std::max(0, cb[0] - 1);
-                ctx->ex_none_rows[1] = cb[1] > cb[0] ? std::min(N, cb[1] + 1) : 1;
-                if (cb[1] <= cb[0]) ctx->ex_none_rows[0] = 0;   // (empty map: one row, no candidate)
+                ec.none_rows[0] = std::max(0, cb[0] - 1);
+                ec.none_rows[1] = cb[1] > cb[0] ? std::min(N, cb[1] + 1) : 1;
+                if (cb[1] <= cb[0]) ec.none_rows[0] = 0;   // (empty map: one row, no candidate)
                 // likewise the columns [cb2 - 1, cb3 + 1): their 64-column words
-                ctx->ex_none_cols[0] = std::max(0, cb[2] - 1) >> 6;
-                ctx->ex_none_cols[1] = cb[3] > cb[2] ? (std::min(N - 1, cb[3]) >> 6) + 1 : 1;
+                ec.none_cols[0] = std::max(0, cb[2] - 1) >> 6;
+                ec.none_cols[1] = cb[3] > cb[2] ? (std::min(N - 1, cb[3]) >> 6) + 1 : 1;
             }
-            ctx->ex_cand = S->cand; ctx->ex_cand_cap = mac_cand_cap(N);
-            ctx->ex_none_host = ctx->opt.mac_noop_host != 0;
-            const int es = extrapolate(ctx, S->X1n, S->X2n, S->phi_pre, dx, dx, P.layers, S->X1n,
-                                       S->X2n, S->flags + 2, S->kbits);
-            ctx->ex_none_wide = false;
-            ctx->ex_none_rows[0] = ctx->ex_none_rows[1] = 0;
-            ctx->ex_none_cols[0] = ctx->ex_none_cols[1] = 0;
-            ctx->ex_cand = nullptr; ctx->ex_cand_cap = 0;
-            ctx->ex_none_host = false;
-            RMT_TRY(es);
+            ec.cand = S->cand; ec.cand_cap = mac_cand_cap(N);
+            ec.none_host = ctx->opt.mac_noop_host != 0;
+            RMT_TRY(extrapolate(ctx, S->X1n, S->X2n, S->phi_pre, dx, dx, P.layers, S->X1n, S->X2n,
+                                S->flags + 2, S->kbits, ec));
             if (!box_mode)
                 k_mac_phi<<<grid1d(n, 256), 256, 0, st>>>(S->X1n, S->X2n, n, P.cx[k], P.cy[k],
                                                           P.R[k], S->X1[k], S->X2[k], S->phi[k],

@@ -142,34 +142,13 @@ struct rmt_ctx {
     // optional kernel timers (rmt_sim profiling): [0,1] around the four RK4 stage kernels,
     // [2,3] around the extrapolation sweep kernel
     bool prof = false;
-    int ex_layers = 0;          // last extrapolation call (rmt_extrap_last_path)
-    bool ex_chain = false;
-    bool ex_par = false;        // the last geometry laid out the parallel mode (extrap_par.hip)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    // optional (sim.hip overlap): recorded on the stream right before the extrapolation's
-    // serial chain kernel starts (or after the call when no chain kernel runs)
-    hipEvent_t ev_chain = nullptr;
-    // optional (sim.hip overlap): extrap_finish leaves the fallback sweep (an early exit unless
-    // a chain capacity limit tripped) to the caller, who runs extrap_sweep on another stream
-    // after ev_chain, beside the chain instead of ahead of it
-    bool ex_sweep_defer = false;
-    // optional (sim.hip overlap, with ex_sweep_defer): ev_chain tracks the completion of the
-    // values pass right before the chain (launch_done) instead of a record of its own
-    bool ev_chain_vals = false;
-    // optional (mac.hip: the extrapolation on the critical stream, where the no-op test finds
-    // nothing to fit as often as not): k_ex_none on a wave per row instead of 64 workgroups
-    bool ex_none_wide = false;
-    // optional (mac.hip box mode): the rows [ex_none_rows[0], ex_none_rows[1]) hold every
-    // candidate target (the known plane is zero outside them); je <= jb: every row
-    int ex_none_rows[2] = {0, 0};
-    int ex_none_cols[2] = {0, 0};   // (and the 64-column words [c0, c1) of those rows)
-    // optional (mac.hip): a candidate list of ex_cand_cap cells + its counter, for the
-    // no-op test's fit-per-wave form (k_ex_cand / k_ex_none_list) under ex_none_wide
-    int *ex_cand = nullptr;
-    int ex_cand_cap = 0;
-    // optional (mac.hip): read the no-op test's verdict back on the host, and when no target
-    // can be accepted skip the rest of the call's launches (the identity: ex_noop_skip)
-    bool ex_none_host = false, ex_noop_skip = false;
+    // what the last extrap_geometry laid out (state, read by extrap_finish, extrap_sweep,
+    // extrap_status and rmt_extrap_last_path; the per-call hints are rmt::ExtrapCall)
+    int ex_layers = 0;
+    bool ex_chain = false;
+    bool ex_par = false;        // the parallel mode (extrap_par.hip)
+    bool ex_noop_skip = false;  // the host read "nothing to fit" (ExtrapCall::none_host)
     // momentum.hip: the stage tiles a full launch's interior kernel skips, per row window
     struct EdgeTiles { int *list = nullptr; int n = 0; long key[6] = {}; };
     EdgeTiles edge[RMT_EDGE_SLOTS];
@@ -186,6 +165,17 @@ struct rmt_ctx {
 static_assert(sizeof(((rmt_ctx *)nullptr)->edge) / sizeof(rmt_ctx::EdgeTiles) == RMT_EDGE_SLOTS, "edge slots");
 
 namespace rmt {
+
+// The context's calls launch on ctx->stream: within this scope on s, afterwards (every exit,
+// an error return included) on the stream it held before.
+struct StreamScope {
+    rmt_ctx *ctx;
+    hipStream_t prev;
+    StreamScope(rmt_ctx *c, hipStream_t s) : ctx(c), prev(c->stream) { c->stream = s; }
+    ~StreamScope() { ctx->stream = prev; }
+    StreamScope(const StreamScope &) = delete;
+    StreamScope &operator=(const StreamScope &) = delete;
+};
 
 int ensure_scratch(rmt_ctx *ctx, size_t bytes);    // >= bytes of double scratch
 int ensure_bytes(rmt_ctx *ctx, size_t bytes);      // >= bytes of byte scratch
@@ -779,26 +769,54 @@ void per_destroy(PerPlan *P);
 void dct_destroy(DctPlan *);
 
 // ------------------------------------------------------------------ extrapolate --
+// One call's optional hints (all off by default); the geometry half reads the none_* / cand
+// fields, the value half the rest.
+struct ExtrapCall {
+    // (sim.hip, slab.hip overlap) recorded on the stream right before the extrapolation's
+    // serial chain kernel starts (or after the call when no chain kernel runs)
+    hipEvent_t chain_event = nullptr;
+    // (sim.hip overlap) extrap_finish leaves the fallback sweep (an early exit unless a chain
+    // capacity limit tripped) to the caller, who runs extrap_sweep on another stream after
+    // chain_event, beside the chain instead of ahead of it
+    bool sweep_deferred = false;
+    // (with sweep_deferred) chain_event tracks the completion of the values pass right before
+    // the chain (launch_done) instead of a record of its own
+    bool event_with_values = false;
+    // (mac.hip: the extrapolation on the critical stream, where the no-op test finds nothing
+    // to fit as often as not) k_ex_none on a wave per row instead of 64 workgroups
+    bool none_wide = false;
+    // (mac.hip box mode) the rows [none_rows[0], none_rows[1]) hold every candidate target (the
+    // known plane is zero outside them); je <= jb: every row
+    int none_rows[2] = {0, 0};
+    int none_cols[2] = {0, 0};   // (and the 64-column words [c0, c1) of those rows)
+    // (mac.hip) a candidate list of cand_cap cells + its counter, for the no-op test's
+    // fit-per-wave form (k_ex_cand / k_ex_none_list) under none_wide
+    int *cand = nullptr;
+    int cand_cap = 0;
+    // (mac.hip) read the no-op test's verdict back on the host, and when no target can be
+    // accepted skip the rest of the call's launches (the identity: rmt_ctx::ex_noop_skip)
+    bool none_host = false;
+};
 // dev_status (optional, device): receives {cells fitted, aborted} after the sweep
 // kin (optional): the known plane (phi < 0) as 64-cell words, ny x ceil(nx/64); phi unused then
 int extrapolate(rmt_ctx *ctx, const double *X1, const double *X2, const double *phi, double dx,
                 double dy, int max_layers, double *X1o, double *X2o, int *dev_status = nullptr,
-                const unsigned long long *kin = nullptr);
+                const unsigned long long *kin = nullptr, const ExtrapCall &call = {});
 // extrapolate() in two halves: the geometry (reads no map value when kin is given and the
 // call is in place) and the values + chain (max_layers > 0; same ctx, nothing else may use
 // ctx->bytes in between)
 int extrap_geometry(rmt_ctx *ctx, const double *X1, const double *X2, const double *phi,
                     double dx, double dy, int max_layers, double *X1o, double *X2o,
-                    const unsigned long long *kin);
+                    const unsigned long long *kin, const ExtrapCall &call = {});
 // the extrapolation's device status words {fitted, aborted} (valid until the next geometry)
 const int *extrap_status(rmt_ctx *ctx, int max_layers);
 // the error message for a nonzero abort word (status[1]; extrap.hpp EXA_*): what timed out,
 // in which chain part, waiting for which producer
 std::string extrap_abort_detail(int code);
 int extrap_finish(rmt_ctx *ctx, double dx, double dy, int max_layers, double *X1o, double *X2o,
-                  int *dev_status);
-// the fallback sweep of the last extrap_finish on stream s (ctx->ex_sweep_defer), ordered after
-// that call's ev_chain; the map and the status words are final once it completes
+                  int *dev_status, const ExtrapCall &call = {});
+// the fallback sweep of the last extrap_finish on stream s (ExtrapCall::sweep_deferred), ordered
+// after that call's chain_event; the map and the status words are final once it completes
 int extrap_sweep(rmt_ctx *ctx, double dx, double dy, int max_layers, double *X1o, double *X2o,
                  hipStream_t s);
 size_t extrap_workspace(int ny, int nx, int max_layers, bool px = false);   // ctx->bytes used
@@ -838,7 +856,8 @@ int slab_rim_extrapolate(rmt_ctx *ctx, const double *gathered, const long long *
                          long long cap, double *X1d, double *X2d, const unsigned long long *bits,
                          double dx, double dy, int layers, int *exflags, double *X1n,
                          double *X2n, long c_lo, long c_hi,
-                         const double *gs = nullptr, hipEvent_t geo = nullptr);
+                         const double *gs = nullptr, hipEvent_t geo = nullptr,
+                         const ExtrapCall &call = {});
 int slab_cols(rmt_ctx *ctx, bool pack, double *Y, int rows, int nx, const int *csplits, int G,
               double *A);
 

@@ -10,6 +10,7 @@
 //   diagnostics: centroid of phi <= 0, J min/max (+ KE, SE, dissipation)
 // State (u, v, p, X1, X2) stays in HBM; one host sync per step reads dt.
 #include "rmt_internal.hpp"
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -883,14 +884,20 @@ int sl_disc_map(rmt_ctx *ctx, const double *X1, const double *X2, const double *
     return RMT_OK;
 }
 
+static DiagArgs diag_args(const rmt_sim_params &P, const double *phi, const double *J,
+                          const double *xs, const double *ys, const double *u, const double *v,
+                          const double *X1, const double *X2, int jb, int je) {
+    return DiagArgs{phi, J, xs, ys, u, v, X1, X2, P.ny, P.nx, P.energies, P.dx, P.dy, P.w_t,
+                    P.rho_s, P.rho_f, P.mu_f, P.eta_s, P.mu_s, P.kappa, jb, je};
+}
+
 // slab-decomposed step: the 10 diagnostic partials of rows [jb, je) into out (device)
 int diag_rows(rmt_ctx *ctx, const double *phi, const double *J, const double *xs,
               const double *ys, const double *u, const double *v, const double *X1,
               const double *X2, const rmt_sim_params &P, int jb, int je, double *part,
               double *out) {
-    DiagArgs D{phi, J, xs, ys, u, v, X1, X2, P.ny, P.nx, P.energies, P.dx, P.dy, P.w_t,
-               P.rho_s, P.rho_f, P.mu_f, P.eta_s, P.mu_s, P.kappa, jb, je};
-    k_diag_p1<<<DIAG_BLOCKS, DIAG_T, 0, ctx->stream>>>(D, part);
+    k_diag_p1<<<DIAG_BLOCKS, DIAG_T, 0, ctx->stream>>>(
+        diag_args(P, phi, J, xs, ys, u, v, X1, X2, jb, je), part);
     k_diag_p2<<<1, DIAG_T, 0, ctx->stream>>>(part, out);
     RMT_LAUNCHED();
     return RMT_OK;
@@ -962,27 +969,36 @@ int rmt_sim_create(rmt_ctx *ctx, const rmt_sim_params *prm, rmt_sim **out) {
             RMT_HIP(hipEventCreateWithFlags(&S->e_in, hipEventDisableTiming));
             RMT_HIP(hipEventCreateWithFlags(&S->e_out, hipEventDisableTiming));
         }
-        RMT_HIP(hipEventCreateWithFlags(&S->e_sl, hipEventDisableTiming));
-        RMT_HIP(hipEventCreateWithFlags(&S->e_mom, hipEventDisableTiming));
-        RMT_HIP(hipEventCreateWithFlags(&S->e_rows, hipEventDisableTiming));
+        for (hipEvent_t *e : {&S->e_sl, &S->e_mom, &S->e_rows})
+            RMT_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
         S->max_tiles = ((nx + MOM_TX - 1) / MOM_TX) * ((ny + MOM_TY - 1) / MOM_TY);
         RMT_HIP(hipMalloc(&S->tiles, (S->max_tiles + 64) * sizeof(int)));
         S->tcount = S->tiles + S->max_tiles;
     }
     S->m2n = ((nx + 255) / 256) * ny;
     const size_t Wn = (size_t)(nx + 63) / 64;
-    RMT_HIP(hipMalloc(&S->m2part, ((size_t)S->m2n + (size_t)RING_N * RING_VALS + ny / 8 + 8 +
-                                   (size_t)ny * Wn + ny / 2 + 8 + (size_t)ny * Wn +
-                                   (size_t)ny * ((nx + 255) / 256) / 2 + 8 + 8 +
-                                   (size_t)S->max_tiles / 8 + 8) * sizeof(double)));
-    S->ring = S->m2part + S->m2n;
-    S->rowmark = (unsigned char *)(S->ring + (size_t)RING_N * RING_VALS);
-    S->rimw = (unsigned long long *)(S->ring + (size_t)RING_N * RING_VALS + ny / 8 + 8);
-    S->rimcnt = (int *)(S->rimw + (size_t)ny * Wn);
-    S->kbits_next = (unsigned long long *)((double *)S->rimcnt + ny / 2 + 8);
-    S->segs = (int *)(S->kbits_next + (size_t)ny * Wn);
-    S->m2acc = (unsigned long long *)(S->segs + (((size_t)ny * ((nx + 255) / 256) + 3) & ~(size_t)1));
-    S->tmark = (unsigned char *)(S->m2acc + 8);   // max_tiles bytes
+    // the second block, carved in this order (sizes in doubles): walked once with no base for
+    // the size and once for the pointers
+    const size_t nseg = (size_t)ny * ((nx + 255) / 256);
+    auto carve = [&](double *base) {
+        size_t o = 0;
+        auto take = [&](auto &p, size_t doubles) {
+            if (base) p = (std::decay_t<decltype(p)>)(base + o);
+            o += doubles;
+        };
+        take(S->m2part, S->m2n);
+        take(S->ring, (size_t)RING_N * RING_VALS);
+        take(S->rowmark, ny / 8 + 8);
+        take(S->rimw, (size_t)ny * Wn);
+        take(S->rimcnt, ny / 2 + 8);
+        take(S->kbits_next, (size_t)ny * Wn);
+        take(S->segs, ((nseg + 3) & ~(size_t)1) / 2);   // nseg ints + the count, to 8 bytes
+        take(S->m2acc, 8);
+        take(S->tmark, (size_t)S->max_tiles / 8 + 8);   // max_tiles bytes
+        return o;
+    };
+    RMT_HIP(hipMalloc(&S->m2part, carve(nullptr) * sizeof(double)));
+    carve(S->m2part);
     RMT_HIP(hipMemsetAsync(S->m2acc, 0, 2 * sizeof(unsigned long long), ctx->stream));
     if (nx % 64 == 0) RMT_HIP(hipMalloc(&S->pconst, (size_t)ny * (nx / 64)));
     if (S->st2 && nx % 64 == 0) {
@@ -990,14 +1006,9 @@ int rmt_sim_create(rmt_ctx *ctx, const rmt_sim_params *prm, rmt_sim **out) {
         RMT_HIP(hipMalloc(&S->zf[0], 2 * ntl));
         S->zf[1] = S->zf[0] + ntl;
     }
-    if (S->st2) {
-        RMT_HIP(hipEventCreateWithFlags(&S->e_bits, hipEventDisableTiming));
-        RMT_HIP(hipEventCreateWithFlags(&S->e_proj, hipEventDisableTiming));
-        RMT_HIP(hipEventCreateWithFlags(&S->e_tail, hipEventDisableTiming));
-        RMT_HIP(hipEventCreateWithFlags(&S->e_tailp, hipEventDisableTiming));
-        RMT_HIP(hipEventCreateWithFlags(&S->e_kb, hipEventDisableTiming));
-        RMT_HIP(hipEventCreateWithFlags(&S->e_geo, hipEventDisableTiming));
-    }
+    if (S->st2)
+        for (hipEvent_t *e : {&S->e_bits, &S->e_proj, &S->e_tail, &S->e_tailp, &S->e_kb, &S->e_geo})
+            RMT_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     if (S->st2 && prm->rho_f > 0) {
         RMT_TRY(dct_plan(ctx, prm->dx, prm->dy));
         S->split_proj = dct_lds_ready(ctx) && ny <= ctx->rsum_len;
@@ -1014,19 +1025,12 @@ int rmt_sim_destroy(rmt_sim *S) {
     if (S->pconst) (void)hipFree(S->pconst);
     if (S->zf[0]) (void)hipFree(S->zf[0]);
     if (S->tiles) (void)hipFree(S->tiles);
-    if (S->e_sl) (void)hipEventDestroy(S->e_sl);
-    if (S->e_mom) (void)hipEventDestroy(S->e_mom);
-    if (S->e_rows) (void)hipEventDestroy(S->e_rows);
-    if (S->e_bits) (void)hipEventDestroy(S->e_bits);
-    if (S->e_proj) (void)hipEventDestroy(S->e_proj);
-    if (S->e_tail) (void)hipEventDestroy(S->e_tail);
-    if (S->e_tailp) (void)hipEventDestroy(S->e_tailp);
-    if (S->e_kb) (void)hipEventDestroy(S->e_kb);
-    if (S->e_geo) (void)hipEventDestroy(S->e_geo);
+    for (hipEvent_t e : {S->e_sl, S->e_mom, S->e_rows, S->e_bits, S->e_proj, S->e_tail,
+                         S->e_tailp, S->e_kb, S->e_geo})
+        if (e) (void)hipEventDestroy(e);
     if (S->st2) (void)hipStreamDestroy(S->st2);
     if (S->st1) (void)hipStreamDestroy(S->st1);
-    if (S->e_in) (void)hipEventDestroy(S->e_in);
-    if (S->e_out) (void)hipEventDestroy(S->e_out);
+    for (hipEvent_t e : {S->e_in, S->e_out}) if (e) (void)hipEventDestroy(e);
     for (auto e : S->pev) if (e) (void)hipEventDestroy(e);
     S->ctx->prof = false;
     delete S;
@@ -1065,147 +1069,647 @@ static int sim_record(rmt_sim *S, const double *dv, double m2, double dt, const 
     return RMT_OK;
 }
 
-int rmt_sim_step(rmt_sim *S, int nsteps, double t_end) {
-    RMT_CHECK(S, RMT_EINVAL, "null sim");
+// The step's schedule, resolved once per call: every decision that depends on the switches
+// (rmt_opts), the shape and the mode but on no value the steps compute.
+struct StepSched {   // (step_sched explains each member where it sets it)
+    bool async, solid, sl, next_bits, par, overlap, rim_split, fixprep, fl_ok, sl_phi, zero_flags,
+        split_proj, early_transpose, skip_marked_rows, side_tail, tail_stream, merged_join,
+        early_geometry, early_diag, diag_first, diag_seg, seg_diag;
+    int delay_side, delay_main;
+};
+
+static StepSched step_sched(const rmt_sim *S, double t_end) {
+    const rmt_opts &o = S->ctx->opt;
+    const rmt_sim_params &P = S->P;
+    const bool nx64 = P.nx % 64 == 0, disc = P.shape == RMT_SHAPE_DISC;
+    StepSched K{};
+    K.sl = P.scheme == RMT_SCHEME_SEMILAGRANGIAN;   // (k_sim_sl writes kbits)
+    // Asynchronous path (no t_end: nothing to clip): dt is computed and consumed on the
+    // device, max |u|^2 comes out of the projection, and the per-step diagnostics go to a
+    // device ring read back every RING_N steps -- no host round trip inside the loop.  The
+    // synchronous path (t_end clip, profiling, the Eulerian schemes) reads dt back each step.
+    K.async = !o.sim_sync && !S->prof && std::isinf(t_end) && t_end > 0 && K.sl;
+    K.solid = P.shape != RMT_SHAPE_NONE;   // the map is advected and extrapolated
+    // this step's phi kernels also write the next step's known plane (split advection)
+    K.next_bits = K.solid && K.sl && S->e_bits && nx64;
+    // the parallel extrapolation: its values pass (~0.5 ms at N=4096, mostly the
+    // one-workgroup combine) runs beside the speculative momentum too (RMT_PAR_OVERLAP=0:
+    // in order, the momentum after it)
+    K.par = extrap_par_enabled();
+    // the extrapolation chain occupies one CU for milliseconds; everything it does not
+    // feed runs beside it: the momentum of every cell, from the pre-extrapolation map, on
+    // a second stream, re-run afterwards on the tiles within reach of a target
+    K.overlap = K.solid && S->st2 && !o.no_overlap && (!K.par || o.par_overlap);
+    // known plane -> rim words -> the rim's advection on the main stream; the rest on the
+    // second stream, beside the extrapolation (which reads rim cells only)
+    K.rim_split = K.sl && K.overlap && S->e_bits;
+    // phi on the fix-up tiles and the momentum's prep there in one kernel (RMT_FUSED_FIXPREP,
+    // default on where nx % 64 == 0), which also copies the extrapolation's status; with it
+    // the fallback sweep runs on the second stream beside the chain (the fix-up joins that
+    // stream before it reads the map or the status)
+    K.fixprep = K.overlap && o.fused_fixprep && disc && nx64 && momentum_mode() != 2 &&
+                P.layers > 0;
+    // k_phi_rebuild writes the momentum's pure-fluid flags (RMT_FUSED_FLUID, default on)
+    K.fl_ok = o.fused_fluid && disc && nx64 && MOM_TX == 64;
+    // the SL pass also leaves phi, the known-plane words and per-tile fluid bits
+    // (RMT_SL_PHI, default on): k_phi_rebuild_fluid's outputs without its pass
+    K.sl_phi = K.sl && S->e_bits && K.fl_ok && o.sl_phi;
+    // the zero-tile flags (sl_zero_flags, with sl_phi): the tiles that stay +0.0 move no map
+    // or phi bytes
+    K.zero_flags = K.sl_phi && S->zf[0] && o.sl_zero_flags;
+    K.split_proj = K.overlap && S->split_proj;   // the projection's row pass beside the chain
+    // the column pass's transpose of the row blocks without fix-up rows beside the chain
+    // (RMT_EARLY_TRANSPOSE, default on)
+    K.early_transpose = K.split_proj && o.early_transpose;
+    K.skip_marked_rows = o.skip_marked_rows != 0;   // (by the speculative row DCT)
+    // (asynchronous path) p -= mean(p) and the diagnostics on the second stream, beside the
+    // next step's chain (RMT_SIDE_TAIL)
+    K.side_tail = K.async && o.side_tail;
+    K.tail_stream = o.tail_stream != 0;   // its pressure update on the edge-tile stream
+    // one join of the second stream instead of two (RMT_MERGED_JOIN, default on; not in
+    // the parallel mode, whose values pass ends long before that stream's row passes):
+    // e_rows, after the speculative momentum AND the projection's rows, ahead of the fix-up
+    // -- beside the ~3 ms chain both are done -- and no second wait before the projection
+    K.merged_join = K.overlap && o.merged_join && !K.par;
+    // the next step's rim words and extrapolation geometry, prepared on the second stream
+    // beside this step's projection (they depend on the known plane alone)
+    K.early_geometry = K.async && o.early_geometry && K.next_bits && P.layers > 0;
+    // this step's diagnostics on the second stream with that geometry.  J is final there
+    // only with the fused fix-up prep (it writes J and records e_kb on completion); without
+    // it momentum_fixup's prep writes J on the main stream later, so the diagnostics stay in
+    // the tail
+    K.early_diag = K.fixprep && K.side_tail && K.split_proj && !P.energies;
+    // ... ahead of the geometry, beside the latency-bound fix-up stages (behind it they
+    // overlapped the projection's DCT passes)
+    K.diag_first = o.diag_first != 0;
+    K.diag_seg = o.diag_seg != 0;   // k_diag_seg where it applies, the fix-up tile marks
+    // the steps' fluid bits and fix-up tile marks are set: k_diag_seg skips segments
+    K.seg_diag = K.overlap && K.sl_phi && K.split_proj && K.diag_seg && !P.energies;
+    K.delay_side = o.test_delay_side;   // k_delay units (tests)
+    K.delay_main = o.test_delay_main;
+    return K;
+}
+
+// What a call's steps hand from one to the next, and one step's phases to each other.
+struct StepRun {
+    hipStream_t st = nullptr;    // the step's stream
+    double *sc = nullptr;        // device scalars: [0] maxsq, [1] dt, [2..11] diag
+    int *ring_flag = nullptr;    // the step flags a ring record takes (null: no shape)
+    // the step's tail (p -= mean(p), the diagnostics) may run on the second stream beside the
+    // next step's band passes; joined before the ring is read and when the call returns.
+    // Deferred to the second stream's next start (the next chain's launch), so that it does
+    // not crowd the next step's rim advection and record values either.
+    bool pending = false;   // a tail waits to be issued (emit_tail), into pend_e
+    bool tail = false;      // an issued tail is not joined yet (e_tail)
+    bool tail_p = false;    // ... and its pressure update ran on the edge-tile stream (e_tailp)
+    double *pend_e = nullptr;
+    // the pending tail's diagnostics already ran (on the second stream after the next step's
+    // geometry, beside the projection: they read phi and J only, final after the fix-up)
+    bool pend_diag_done = false, diag_early = false;
+    // the last step's ring record, completed by the next step's k_dt_part (or by flush)
+    double *ring_e = nullptr;
+    int slot = 0;             // ring records since the last read-back
+    bool geo_ready = false;   // the next extrapolation's geometry is on its way (e_geo)
+    bool early_t = false;     // the unmarked row blocks are transposed already
+    bool m2_last = false;     // the last step's projection wrote the max |u|^2 partials
+    // this step: dt on the host (synchronous path; hv: the read-back {maxsq, dt}) or on the
+    // device (dtp), the momentum's parameters and work planes, the buffer of the next known
+    // plane (null: none written), the zero-tile flags of the map's output buffer hold
+    double hv[2] = {0.0, 0.0}, dt = NAN;
+    const double *dtp = nullptr;
+    rmt_momentum_params M{};
+    MomWork W{};
+    unsigned long long *nb = nullptr;
+    bool zo_valid = false;
+};
+
+// the whole grid's diagnostics with the map in (X1, X2); seg: with this step's fluid bits and
+// fix-up tile marks (StepSched::seg_diag, second-stream diagnostics only)
+static DiagArgs step_diag_args(const rmt_sim *S, const double *X1, const double *X2, bool seg) {
+    DiagArgs D = diag_args(S->P, S->phi, S->J, S->xs, S->ys, S->u, S->v, X1, X2, 0, S->P.ny);
+    if (seg) {
+        D.fbits = fluid_bits_buf(mom_work(S->mw, (long)S->P.ny * S->P.nx, S->mbytes, S->flag + 1));
+        D.tmark = S->tmark;
+    }
+    return D;
+}
+
+// The pending tail.  after_sl: the second stream already waits for this step's e_sl, recorded
+// on the main stream after the tail's projection -- no event of its own (a record right after
+// the velocity correction cost the critical path ~5 us); else one recorded now
+static int emit_tail(rmt_sim *S, const StepSched &K, StepRun &R, bool after_sl) {
+    if (!R.pending) return RMT_OK;
+    R.pending = false;
+    rmt_ctx *ctx = S->ctx;
+    const int ny = S->P.ny, nx = S->P.nx;
+    const DiagArgs D = step_diag_args(S, S->X1, S->X2, K.seg_diag);
+    if (!after_sl) {
+        RMT_HIP(hipEventRecord(S->e_proj, R.st));
+        RMT_HIP(hipStreamWaitEvent(S->st2, S->e_proj, 0));
+    }
+    // beside the chain (after_sl), the pressure update runs on the edge-tile stream,
+    // beside the second stream's SL and prep; that stream's momentum stages wait for it
+    // (tail_p, MomWork::wait_p) before they read p, and nothing else of the step touches
+    // p, pc or the root before then (RMT_TAIL_STREAM)
+    hipStream_t ts_st = S->st2;
+    if (after_sl && K.tail_stream) {
+        StreamScope on(ctx, S->st2);   // (the edge-tile stream of the second stream's priority)
+        hipStream_t es = nullptr;
+        RMT_TRY(edge_stream(ctx, &es));
+        if (es) {
+            RMT_HIP(hipStreamWaitEvent(es, S->e_sl, 0));
+            ts_st = es;
+        }
+    }
+    {
+        // (the pending tail always follows a projection_finish that deferred the pressure
+        // update: pc and its mean's root are still where that projection left them)
+        StreamScope on(ctx, ts_st);
+        RMT_TRY(sub_mean_rows_upd(ctx, S->p, ctx->scratch + (long)ny * nx,
+                                  ctx->red + RED_BLOCKS + 17, ny, nx));
+    }
+    R.tail_p = ts_st != S->st2;
+    if (R.tail_p) RMT_HIP(hipEventRecord(S->e_tailp, ts_st));
+    if (!R.pend_diag_done) {
+        // (this step's SL pass and fix-up marks come after this on the same stream)
+        diag_partials(D, S->dscr, S->st2, K.diag_seg);
+        k_diag_p2<<<1, DIAG_T, 0, S->st2>>>(S->dscr, R.pend_e);
+        RMT_LAUNCHED();
+    }
+    RMT_HIP(hipEventRecord(S->e_tail, S->st2));
+    R.tail = true;
+    return RMT_OK;
+}
+
+static int join(rmt_sim *S, const StepSched &K, StepRun &R) {
+    RMT_TRY(emit_tail(S, K, R, false));
+    if (R.tail) RMT_HIP(hipStreamWaitEvent(R.st, S->e_tail, 0));
+    if (R.tail && R.tail_p) RMT_HIP(hipStreamWaitEvent(R.st, S->e_tailp, 0));
+    R.tail = false;
+    R.tail_p = false;
+    return RMT_OK;
+}
+
+// join the tail, complete the last ring record and book the ring's records on the host
+static int flush(rmt_sim *S, const StepSched &K, StepRun &R) {
+    RMT_TRY(join(S, K, R));
+    if (R.ring_e) {
+        k_ring_put<<<1, 64, 0, R.st>>>(R.sc, R.ring_flag, R.ring_e);
+        RMT_LAUNCHED();
+        R.ring_e = nullptr;
+    }
+    if (!R.slot) return RMT_OK;
+    std::vector<double> h((size_t)R.slot * RING_VALS);
+    RMT_HIP(hipMemcpyAsync(h.data(), S->ring, h.size() * sizeof(double), hipMemcpyDeviceToHost,
+                           R.st));
+    RMT_HIP(hipStreamSynchronize(R.st));
+    const int cnt = R.slot;
+    R.slot = 0;
+    for (int k = 0; k < cnt; ++k) {
+        const double *e = h.data() + (size_t)k * RING_VALS;
+        int fl[4];
+        for (int q = 0; q < 4; ++q) fl[q] = (int)e[DIAG_VALS + 2 + q];
+        RMT_TRY(sim_record(S, e, e[DIAG_VALS], e[DIAG_VALS + 1], fl));
+    }
+    return RMT_OK;
+}
+
+// the rim words of the known plane `bits` and their row segments on stream s; with
+// `geometry` also the extrapolation geometry of that plane (the next step's)
+static int rim_geometry(rmt_sim *S, const unsigned long long *bits, hipStream_t s,
+                        bool geometry) {
+    rmt_ctx *ctx = S->ctx;
+    const rmt_sim_params &P = S->P;
+    const long nseg = (long)P.ny * ((P.nx + 255) / 256);
+    int *scount = S->segs + nseg;
+    StreamScope on(ctx, s);
+    RMT_TRY(rim_words(ctx, bits, P.ny, P.nx, (P.nx + 63) / 64, S->rimw, S->rimcnt));
+    RMT_HIP(hipMemsetAsync(scount, 0, sizeof(int), s));
+    k_rim_segments<<<grid1d(nseg, 256), 256, 0, s>>>(S->rimw, P.ny, P.nx, S->segs, scount);
+    if (geometry)
+        RMT_TRY(extrap_geometry(ctx, S->X1n, S->X2n, nullptr, P.dx, P.dy, P.layers, S->X1n,
+                                S->X2n, bits));
+    return RMT_OK;
+}
+
+// phi from the advected + extrapolated map on stream s, with the next step's known plane;
+// where the fluid flags are fused (fl_ok) the momentum's pure-fluid flags in the same pass
+static int phi_rebuild(rmt_sim *S, const StepSched &K, const StepRun &R, hipStream_t s,
+                       MomWork &W) {
+    const rmt_sim_params &P = S->P;
+    const long n = (long)P.ny * P.nx;
+    if (K.fl_ok) {
+        k_phi_rebuild_fluid<<<grid1d(n, 256), 256, 0, s>>>(
+            S->X1n, S->X2n, n, P.nx, (P.nx + 63) / 64, P.x0, P.y0, P.R, S->phi, nullptr, nullptr,
+            R.nb, fluid_threshold(&R.M), fluid_rows_buf(W, 0, P.nx));
+        W.fluid_rows_ready = true;
+    } else {
+        k_phi_rebuild<<<grid1d(n, 256), 256, 0, s>>>(S->X1n, S->X2n, n, P.shape, P.x0, P.y0, P.R,
+                                                      S->phi, nullptr, nullptr, R.nb);
+    }
+    RMT_LAUNCHED();
+    return RMT_OK;
+}
+
+// the next step's known plane is the one this step's phi kernels wrote
+static void advance_known_plane(rmt_sim *S, const unsigned long long *nb) {
+    if (nb) { std::swap(S->kbits, S->kbits_next); S->bits_ready = true; }
+}
+
+// 1. dt (compute_timestep + the drivers' clip to t_end); NaN-propagating max so it also bounds
+// the velocities for the SL block skip.  have_m2: the last projection left its max |u|^2
+// partials.  Then what the step's other phases take from dt.
+static int step_dt(rmt_sim *S, const StepSched &K, StepRun &R, bool have_m2, double t_end) {
+    rmt_ctx *ctx = S->ctx;
+    const rmt_sim_params &P = S->P;
+    const long n = (long)P.ny * P.nx;
+    R.hv[0] = R.hv[1] = 0.0;
+    R.dt = NAN;
+    if (K.async && have_m2) {
+        k_dt_part<<<DTP_BLOCKS, 256, 0, R.st>>>(S->m2part, S->m2n, S->dt_const, P.cfl, P.dx, R.sc,
+                                                S->m2acc, R.ring_e ? R.ring_flag : nullptr,
+                                                R.ring_e);
+        RMT_LAUNCHED();
+        R.ring_e = nullptr;
+    } else {
+        RMT_CHECK(!R.ring_e, RMT_EINVAL, "sim: ring record pending on a synchronous step");
+        RMT_TRY(reduce_maxsq2_nan(ctx, S->u, S->v, n, R.sc));
+        k_dt<<<1, 1, 0, R.st>>>(R.sc, S->dt_const, P.cfl, P.dx, R.sc + 1);
+        RMT_LAUNCHED();
+    }
+    if (!K.async) {
+        RMT_HIP(hipMemcpyAsync(R.hv, R.sc, 2 * sizeof(double), hipMemcpyDeviceToHost, R.st));
+        RMT_HIP(hipStreamSynchronize(R.st));
+        R.dt = R.hv[1];
+        if (S->t + R.dt > t_end) R.dt = t_end - S->t;
+    }
+    R.dtp = K.async ? R.sc + 1 : nullptr;
+    R.nb = K.next_bits ? S->kbits_next : nullptr;
+    rmt_momentum_params &M = R.M;
+    M.bc_kind = P.bc_kind; M.lid = P.lid; M.mu_s = P.mu_s; M.kappa = P.kappa;
+    M.eta_s = P.eta_s; M.rho_s = P.rho_s; M.rho_f = P.rho_f; M.mu_f = P.mu_f; M.w_t = P.w_t;
+    M.dx = P.dx; M.dy = P.dy; M.dt = R.dt; M.stress_band = P.stress_band;
+    M.detg_clamp = P.detg_clamp;
+    R.W = mom_work(S->mw, n, S->mbytes, S->flag + 1);
+    R.W.dtp = R.dtp;
+    R.W.prep_const = S->pconst;
+    return RMT_OK;
+}
+
+// 2. advect the reference map with the pre-advection level set and mask
+static int step_advect(rmt_sim *S, const StepSched &K, StepRun &R, bool first) {
     rmt_ctx *ctx = S->ctx;
     const rmt_sim_params &P = S->P;
     const int ny = P.ny, nx = P.nx;
     const long n = (long)ny * nx;
     const unsigned g = grid1d(n, 256);
-    // run on S->st1 (highest priority) when it exists: ordered after the caller's stream on
-    // entry, the caller's stream ordered after it on every return
-    struct OnHi {
-        rmt_ctx *c; hipStream_t user; rmt_sim *S;
-        ~OnHi() {
-            if (!S->st1) return;
-            (void)hipEventRecord(S->e_out, S->st1);
-            (void)hipStreamWaitEvent(user, S->e_out, 0);
-            c->stream = user;
+    hipStream_t st = R.st;
+    const double dt = R.dt;
+    // (the output buffer's zero-tile flags hold only when the flagged pass writes it;
+    // the flagged pass reads them first: the rim pass and the chain below write only rim
+    // cells, and a tile with a rim cell never uses them)
+    R.zo_valid = S->zv[S->zcur ^ 1];
+    S->zv[S->zcur ^ 1] = false;
+    // (on the asynchronous path the previous step's ring record -- k_dt_part or k_ring_put --
+    // cleared it)
+    if (!(K.async && !first)) RMT_HIP(hipMemsetAsync(S->flag, 0, sizeof(int), st));
+    if (K.rim_split) {
+        const dim3 gsl((nx + 255) / 256, ny);
+        if (!S->bits_ready) {
+            k_sim_bits<<<gsl, 256, 0, st>>>(S->X1, S->X2, nx, P.x0, P.y0, P.R, S->kbits);
+            RMT_LAUNCHED();
         }
-    } on_hi{ctx, ctx->stream, S};
-    // the map buffers swap roles every step; at the call's end the state is copied back into
-    // the buffers rmt_sim_field hands out (one copy per call instead of one per step).  Runs
-    // on the step's stream before on_hi hands the stream back (destroyed first).
-    struct MapHome {
-        rmt_sim *S;
-        ~MapHome() {
-            if (S->X1 == S->X1h) return;
-            const size_t b = (size_t)S->P.ny * S->P.nx * sizeof(double);
-            (void)hipMemcpyAsync(S->X1h, S->X1, b, hipMemcpyDeviceToDevice, S->ctx->stream);
-            (void)hipMemcpyAsync(S->X2h, S->X2, b, hipMemcpyDeviceToDevice, S->ctx->stream);
-            std::swap(S->X1, S->X1n);
-            std::swap(S->X2, S->X2n);
-            S->zcur ^= 1;
+        if (R.geo_ready)
+            RMT_HIP(hipStreamWaitEvent(st, S->e_geo, 0));
+        else
+            RMT_TRY(rim_geometry(S, S->kbits, st, false));
+        const long nseg = (long)ny * ((nx + 255) / 256);
+        k_sim_sl_rim<<<4096, 256, 0, st>>>(   // ~one rim segment per block
+            S->X1, S->X2, S->u, S->v, S->xs, S->ys, ny, nx, dt, divk_make(P.dx), divk_make(P.dy), P.x0, P.y0,
+            P.R, S->X1n, S->X2n, S->flag, R.sc, R.dtp, S->rimw, S->segs, S->segs + nseg);
+    } else if (K.sl) {
+        k_sim_sl_t<0><<<dim3((nx + SLT_X - 1) / SLT_X, (ny + SLT_Y - 1) / SLT_Y), SLT_X * SLT_Y,
+                     0, st>>>(S->X1, S->X2, S->u, S->v, S->xs, S->ys, ny, nx, dt,
+                              divk_make(P.dx), divk_make(P.dy), P.x0, P.y0, P.R, S->X1n,
+                              S->X2n, S->phi_pre, S->flag, S->kbits, R.sc, R.dtp, 0, nullptr);
+    } else if (P.scheme == RMT_SCHEME_SEMILAGRANGIAN_CUBIC) {
+        k_sim_sl_cubic<<<g, 256, 0, st>>>(S->X1, S->X2, S->u, S->v, S->xs, S->ys, ny, nx, dt,
+                                          P.dx, P.dy, P.x0, P.y0, P.R, S->X1n, S->X2n,
+                                          S->phi_pre, S->flag);
+    } else {
+        // Eulerian schemes on the pre-advection level set, w_cut = 0 as the drivers
+        k_sim_phi_mask<<<g, 256, 0, st>>>(S->X1, S->X2, S->u, S->v, n, P.x0, P.y0, P.R,
+                                          S->phi_pre, S->flag);
+        for (int comp = 0; comp < 2; ++comp) {
+            const double *q = comp ? S->X2 : S->X1;
+            double *o = comp ? S->X2n : S->X1n;
+            if (P.scheme == RMT_SCHEME_WENO5)
+                RMT_TRY(rmt_advect_weno5_rk3(ctx, q, S->u, S->v, P.dx, P.dy, dt, S->phi_pre, 0.0,
+                                             o));
+            else
+                RMT_TRY(rmt_advect_central_rk3(ctx, q, S->u, S->v, P.dx, P.dy, dt, S->phi_pre,
+                                               0.0, P.scheme == RMT_SCHEME_CONSERVATIVE, o));
         }
-    } map_home{S};
-    if (S->st1) {
-        RMT_HIP(hipEventRecord(S->e_in, ctx->stream));
-        RMT_HIP(hipStreamWaitEvent(S->st1, S->e_in, 0));
-        ctx->stream = S->st1;
+        k_mask_mul<<<g, 256, 0, st>>>(S->X1n, S->X2n, S->phi_pre, n);
     }
-    hipStream_t st = ctx->stream;
-    double *sc = S->dscr + DIAG_BLOCKS * DIAG_VALS;   // [0] maxsq, [1] dt, [2..11] diag
-    // Asynchronous path (no t_end: nothing to clip): dt is computed and consumed on the
-    // device, max |u|^2 comes out of the projection, and the per-step diagnostics go to a
-    // device ring read back every RING_N steps -- no host round trip inside the loop.  The
-    // synchronous path (t_end clip, profiling, the Eulerian schemes) reads dt back each step.
-    const bool force_sync = ctx->opt.sim_sync != 0;
-    const bool async = !force_sync && !S->prof && std::isinf(t_end) && t_end > 0 &&
-                       P.scheme == RMT_SCHEME_SEMILAGRANGIAN;
-    int slot = 0;
-    // the step's tail (p -= mean(p), the diagnostics) may run on the second stream beside the
-    // next step's band passes; joined before the ring is read and when the call returns
-    // Deferred to the second stream's next start (the next chain's launch), so that it does
-    // not crowd the next step's rim advection and record values either.
-    bool tail = false, pending = false;
-    bool tail_p = false;   // the pending tail's pressure update ran on the edge-tile stream
-    double *pend_e = nullptr;
-    // the pending tail's diagnostics already ran (on the second stream after the next step's
-    // geometry, beside the projection: they read phi and J only, final after the fix-up)
-    bool pend_diag_done = false, diag_early = false, pend_seg = false;
-    // after_sl: the second stream already waits for this step's e_sl, recorded on the main
-    // stream after the tail's projection -- no event of its own (a record right after the
-    // velocity correction cost the critical path ~5 us); else one recorded now
-    auto emit_tail = [&](bool after_sl) -> int {
-        if (!pending) return RMT_OK;
-        pending = false;
-        DiagArgs D{S->phi, S->J, S->xs, S->ys, S->u, S->v, S->X1, S->X2, ny, nx, P.energies,
-                   P.dx, P.dy, P.w_t, P.rho_s, P.rho_f, P.mu_f, P.eta_s, P.mu_s, P.kappa, 0, ny};
-        if (!after_sl) {
-            RMT_HIP(hipEventRecord(S->e_proj, st));
-            RMT_HIP(hipStreamWaitEvent(S->st2, S->e_proj, 0));
+    RMT_LAUNCHED();
+    return RMT_OK;
+}
+
+// 3. narrow-band extrapolation (exact raster-order semantics), in place; with the overlap,
+// the second stream's work of this step starts once the chip-wide passes are done and the
+// one-workgroup chain kernel is launched (e_sl)
+static int step_extrapolate(rmt_sim *S, const StepSched &K, StepRun &R) {
+    rmt_ctx *ctx = S->ctx;
+    const rmt_sim_params &P = S->P;
+    ExtrapCall ec;
+    if (K.overlap) ec.chain_event = S->e_sl;
+    if (R.geo_ready && !K.overlap) RMT_HIP(hipStreamWaitEvent(R.st, S->e_geo, 0));
+    // with the fused fix-up prep the status words are copied by its kernel, the fallback
+    // sweep is left to the second stream, and e_sl completes with the values pass
+    int *dstat = K.fixprep ? nullptr : S->flag + 2;
+    ec.sweep_deferred = ec.event_with_values = K.fixprep;
+    const bool prepared = R.geo_ready && P.layers > 0;
+    R.geo_ready = false;
+    if (prepared)
+        RMT_TRY(extrap_finish(ctx, P.dx, P.dy, P.layers, S->X1n, S->X2n, dstat, ec));
+    else
+        RMT_TRY(extrapolate(ctx, S->X1n, S->X2n, S->phi_pre, P.dx, P.dy, P.layers, S->X1n,
+                            S->X2n, dstat, K.sl ? S->kbits : nullptr, ec));
+    if (K.overlap) RMT_HIP(hipStreamWaitEvent(S->st2, S->e_sl, 0));
+    return RMT_OK;
+}
+
+// Everything queued on the second stream beside the chain: the deferred sweep, the previous
+// step's tail, the fix-up tiles and the rows they reach, the advection of the non-rim cells,
+// phi, the speculative momentum, the projection's rows from it and the early transpose.
+static int step_side_stream(rmt_sim *S, const StepSched &K, StepRun &R) {
+    rmt_ctx *ctx = S->ctx;
+    const rmt_sim_params &P = S->P;
+    const int ny = P.ny, nx = P.nx;
+    const long n = (long)ny * nx;
+    hipStream_t s2 = S->st2;
+    if (K.delay_side) { k_delay<<<1, 1, 0, s2>>>(K.delay_side); RMT_LAUNCHED(); }
+    if (K.fixprep && ctx->ex_chain && !ctx->ex_par)
+        RMT_TRY(extrap_sweep(ctx, P.dx, P.dy, P.layers, S->X1n, S->X2n, s2));
+    // the previous step's tail, beside the chain (e_sl, recorded by this step's
+    // extrapolation when it has layers, follows that step's projection)
+    RMT_TRY(emit_tail(S, K, R, P.layers > 0));
+    // the fix-up tiles and the rows they reach depend on the known plane only
+    {
+        StreamScope on(ctx, s2);
+        RMT_TRY(extrap_fix_tiles(ctx, P.layers, 12, S->tiles, S->tcount));
+    }
+    if (K.split_proj) {
+        RMT_HIP(hipMemsetAsync(S->rowmark, 0, ny, s2));
+        if (K.diag_seg) RMT_HIP(hipMemsetAsync(S->tmark, 0, S->max_tiles, s2));
+        k_mark_rows<<<list_grid(S->max_tiles), 64, 0, s2>>>(
+            S->tiles, S->tcount, (nx + MOM_TX - 1) / MOM_TX, ny, S->rowmark,
+            K.diag_seg ? S->tmark : nullptr);
+        RMT_LAUNCHED();
+    }
+    MomWork Wf = R.W;
+    if (R.tail_p) Wf.wait_p = S->e_tailp;   // (emit_tail above: p on another stream)
+    if (K.sl && S->e_bits) {
+        // the advection of every non-rim cell, once the chain has started (earlier its
+        // blocks would crowd out the one-workgroup band passes)
+        const bool zon = K.zero_flags;
+        const int zi = S->zcur, zo = S->zcur ^ 1;
+        k_sim_sl_t<0><<<dim3((nx + SLT_X - 1) / SLT_X, (ny + SLT_Y - 1) / SLT_Y),
+                     SLT_X * SLT_Y, 0, s2>>>(
+            S->X1, S->X2, S->u, S->v, S->xs, S->ys, ny, nx, R.dt, divk_make(P.dx),
+            divk_make(P.dy), P.x0, P.y0, P.R, S->X1n, S->X2n, S->phi_pre, S->flag,
+            nullptr, R.sc, R.dtp, 2, S->rimw, K.sl_phi ? S->phi : nullptr,
+            fluid_threshold(&R.M), K.sl_phi ? fluid_bits_buf(R.W) : nullptr,
+            K.sl_phi ? R.nb : nullptr, 0, 0, zon && S->zv[zi] ? S->zf[zi] : nullptr,
+            zon ? S->zf[zo] : nullptr, zon && R.zo_valid);
+        RMT_LAUNCHED();
+        S->zv[zo] = zon;
+    }
+    if (K.sl_phi)
+        Wf.fluid_bits = fluid_bits_buf(R.W);
+    else   // phi (and the stage kernels' pure-fluid flags) in a pass of its own
+        RMT_TRY(phi_rebuild(S, K, R, s2, Wf));
+    {
+        StreamScope on(ctx, s2);
+        RMT_TRY(momentum_rk4(ctx, &R.M, S->u, S->v, S->p, S->X1n, S->X2n, S->phi, S->us, S->vs,
+                             S->sxx, S->sxy, S->syy, S->J, Wf));
+        RMT_HIP(hipEventRecord(S->e_mom, s2));
+        // and the projection's rows from the speculative u*, v* (the fix-up tiles the
+        // main stream re-runs meanwhile only feed rows it redoes afterwards)
+        if (K.split_proj)
+            RMT_TRY(projection_rows(ctx, S->us, S->vs, P.dx, P.dy, R.dtp, R.dt, P.rho_f, S->p,
+                                    nullptr, nullptr, nullptr, 0,
+                                    K.skip_marked_rows ? S->rowmark : nullptr));
+        // and the row blocks no fix-up row falls in, transposed for the column pass
+        if (K.early_transpose) {
+            RMT_TRY(dct_transpose_unmarked(ctx, ctx->scratch + n, S->rowmark));
+            R.early_t = true;
         }
-        ctx->stream = S->st2;
-        // beside the chain (after_sl), the pressure update runs on the edge-tile stream,
-        // beside the second stream's SL and prep; that stream's momentum stages wait for it
-        // (tail_p, MomWork::wait_p) before they read p, and nothing else of the step touches
-        // p, pc or the root before then (RMT_TAIL_STREAM)
-        hipStream_t ts_st = S->st2;
-        if (after_sl && ctx->opt.tail_stream) {
-            hipStream_t es = nullptr;
-            const int e = edge_stream(ctx, &es);
-            if (e != RMT_OK) { ctx->stream = st; return e; }
-            if (es) {
-                RMT_HIP(hipStreamWaitEvent(es, S->e_sl, 0));
-                ts_st = es;
-            }
+    }
+    RMT_HIP(hipEventRecord(S->e_rows, s2));
+    return RMT_OK;
+}
+
+// this step's diagnostics (phi, J: final after the fix-up prep) on stream s, beside the
+// projection, instead of in the tail beside the next chain; they land in the ring slot this
+// step's record takes in step_record
+static int diag_early(rmt_sim *S, const StepSched &K, StepRun &R, hipStream_t s) {
+    const DiagArgs D = step_diag_args(S, S->X1n, S->X2n, K.seg_diag);
+    diag_partials(D, S->dscr, s, K.diag_seg);
+    k_diag_p2<<<1, DIAG_T, 0, s>>>(S->dscr, S->ring + (size_t)R.slot * RING_VALS);
+    R.diag_early = true;
+    RMT_LAUNCHED();
+    return RMT_OK;
+}
+
+// 4 + 5 with the overlap: phi and the momentum again on the tiles the extrapolation can
+// reach.  more: a step follows (in this call or, carried, the next)
+static int step_fixup(rmt_sim *S, const StepSched &K, StepRun &R, bool more) {
+    rmt_ctx *ctx = S->ctx;
+    const rmt_sim_params &P = S->P;
+    const int ny = P.ny, nx = P.nx;
+    hipStream_t st = R.st;
+    if (K.delay_main) { k_delay<<<1, 1, 0, st>>>(K.delay_main); RMT_LAUNCHED(); }
+    RMT_HIP(hipStreamWaitEvent(st, K.merged_join ? S->e_rows : S->e_mom, 0));
+    // the next step's geometry below starts once the known plane is final (e_kb)
+    const bool geo_next = K.early_geometry && more;
+    if (K.fixprep) {
+        RMT_TRY(fixup_phi_prep(ctx, &R.M, R.W, S->X1n, S->X2n, P.x0, P.y0, P.R, nullptr, nullptr,
+                               S->phi, R.nb, S->sxx, S->sxy, S->syy, S->J, S->tiles, S->tcount,
+                               S->max_tiles, extrap_status(ctx, P.layers), S->flag + 2,
+                               geo_next ? S->e_kb : nullptr));
+    } else {
+        k_phi_tiles<<<list_grid(S->max_tiles), 256, 0, st>>>(
+            S->X1n, S->X2n, ny, nx, P.x0, P.y0, P.R, S->phi, nullptr, nullptr, S->tiles,
+            S->tcount, (nx + MOM_TX - 1) / MOM_TX, R.nb);
+        RMT_LAUNCHED();
+    }
+    if (geo_next) {
+        // the next step's known plane is final (the phi kernel above): its rim words, rim
+        // segments and extrapolation geometry on the second stream, beside the rest of
+        // this step (nothing there uses them or the extrapolation workspace).  Issued
+        // before the fix-up stages: after them its few-block kernels would share the CUs
+        // with the projection's FFT passes (measured: the step no faster)
+        hipStream_t sg = S->st2;
+        if (!K.fixprep) RMT_HIP(hipEventRecord(S->e_kb, st));   // (else: with the prep)
+        RMT_HIP(hipStreamWaitEvent(sg, S->e_kb, 0));
+        if (K.early_diag && K.diag_first) RMT_TRY(diag_early(S, K, R, sg));
+        RMT_TRY(rim_geometry(S, R.nb, sg, true));
+        RMT_HIP(hipEventRecord(S->e_geo, sg));
+        R.geo_ready = true;
+        if (K.early_diag && !K.diag_first) RMT_TRY(diag_early(S, K, R, sg));
+    }
+    return momentum_fixup(ctx, &R.M, S->u, S->v, S->p, S->X1n, S->X2n, S->phi, S->us, S->vs,
+                          S->sxx, S->sxy, S->syy, S->J, R.W, S->tiles, S->tcount, S->max_tiles,
+                          nullptr, K.fixprep);
+}
+
+// 4 + 5 in order.  more: another step of this call follows
+static int step_inorder(rmt_sim *S, const StepSched &K, StepRun &R, bool more) {
+    rmt_ctx *ctx = S->ctx;
+    const rmt_sim_params &P = S->P;
+    // 4. phi from the advected + extrapolated map (and the momentum's pure-fluid flags)
+    RMT_TRY(phi_rebuild(S, K, R, R.st, R.W));
+    if (K.par && K.early_geometry && S->st2 && more) {
+        // the next step's extrapolation geometry (known plane nb) beside this step's
+        // momentum and projection
+        RMT_HIP(hipEventRecord(S->e_kb, R.st));
+        RMT_HIP(hipStreamWaitEvent(S->st2, S->e_kb, 0));
+        {
+            StreamScope on(ctx, S->st2);
+            RMT_TRY(extrap_geometry(ctx, S->X1n, S->X2n, nullptr, P.dx, P.dy, P.layers, S->X1n,
+                                    S->X2n, R.nb));
         }
-        ctx->stream = ts_st;
-        // (the pending tail always follows a projection_finish that deferred the pressure
-        // update: pc and its mean's root are still where that projection left them)
-        const int ts = sub_mean_rows_upd(ctx, S->p, ctx->scratch + (long)ny * nx,
-                                         ctx->red + RED_BLOCKS + 17, ny, nx);
-        ctx->stream = st;
-        RMT_TRY(ts);
-        tail_p = ts_st != S->st2;
-        if (tail_p) RMT_HIP(hipEventRecord(S->e_tailp, ts_st));
-        if (!pend_diag_done) {
-            // (this step's SL pass and fix-up marks come after this on the same stream)
-            if (pend_seg) {
-                D.fbits = fluid_bits_buf(mom_work(S->mw, (long)ny * nx, S->mbytes, S->flag + 1));
-                D.tmark = S->tmark;
-            }
-            diag_partials(D, S->dscr, S->st2, ctx->opt.diag_seg != 0);
-            k_diag_p2<<<1, DIAG_T, 0, S->st2>>>(S->dscr, pend_e);
-            RMT_LAUNCHED();
-        }
-        RMT_HIP(hipEventRecord(S->e_tail, S->st2));
-        tail = true;
+        RMT_HIP(hipEventRecord(S->e_geo, S->st2));
+        R.geo_ready = true;
+    }
+    // 5. momentum (RK4)
+    return momentum_rk4(ctx, &R.M, S->u, S->v, S->p, S->X1n, S->X2n, S->phi, S->us, S->vs,
+                        S->sxx, S->sxy, S->syy, S->J, R.W);
+}
+
+// 6. projection (constant density rho_f; Neumann DCT-I)
+static int step_project(rmt_sim *S, const StepSched &K, StepRun &R) {
+    rmt_ctx *ctx = S->ctx;
+    const rmt_sim_params &P = S->P;
+    if (K.split_proj) {
+        // redo the rhs on the fix-up tiles (+1 cell) and the row DCT of the rows they
+        // reach, then the column pass and the rest
+        if (!K.merged_join) RMT_HIP(hipStreamWaitEvent(R.st, S->e_rows, 0));
+        RMT_TRY(projection_rows(ctx, S->us, S->vs, P.dx, P.dy, R.dtp, R.dt, P.rho_f, S->p,
+                                S->rowmark, S->tiles, S->tcount, S->max_tiles));
+        RMT_TRY(projection_finish(ctx, S->us, S->vs, P.dx, P.dy, R.dtp, R.dt, P.rho_f, P.bc_kind,
+                                  P.lid, S->p, S->u, S->v, S->p, K.async ? S->m2part : nullptr,
+                                  !K.side_tail, R.early_t ? S->rowmark : nullptr));
+        R.early_t = false;
+    } else if (K.async) {
+        RMT_TRY(projection_dev(ctx, S->us, S->vs, P.dx, P.dy, R.dtp, P.rho_f, P.bc_kind, P.lid,
+                               S->p, S->u, S->v, S->p, S->m2part));
+    } else {
+        RMT_TRY(rmt_pressure_projection(ctx, S->us, S->vs, P.dx, P.dy, R.dt, P.rho_f, P.bc_kind,
+                                        P.lid, S->p, S->u, S->v, S->p));
+    }
+    R.m2_last = K.async;
+    // the advected + extrapolated map (X1n, X2n) is the state from here on: the two map
+    // buffers swap roles instead of copying the map back (restored at the call's end)
+    std::swap(S->X1, S->X1n);
+    std::swap(S->X2, S->X2n);
+    S->zcur ^= 1;
+    return RMT_OK;
+}
+
+// 7. diagnostics (running them beside the projection on the second stream measured no gain:
+// both are HBM-bound) and the step's record: a pending tail, a ring record, or read back now
+static int step_record(rmt_sim *S, const StepSched &K, StepRun &R) {
+    hipStream_t st = R.st;
+    double *e = S->ring + (size_t)R.slot * RING_VALS;
+    if (K.side_tail && K.split_proj) {
+        // p -= mean(p) and the diagnostics on the second stream: nothing before the next
+        // step's chain reads p or writes what they read (that stream's next work -- the
+        // speculative phi, momentum -- is queued behind them)
+        R.pend_e = e;
+        R.pending = true;
+        R.pend_diag_done = R.diag_early;
+        R.diag_early = false;
+    } else {
+        diag_partials(step_diag_args(S, S->X1, S->X2, false), S->dscr, st, K.diag_seg);
+        k_diag_p2<<<1, DIAG_T, 0, st>>>(S->dscr, K.async ? e : R.sc + 2);
+        RMT_LAUNCHED();
+    }
+    if (K.async) {
+        R.ring_e = e;
+        advance_known_plane(S, R.nb);
+        if (++R.slot == S->sync_every) RMT_TRY(flush(S, K, R));
         return RMT_OK;
-    };
-    auto join = [&]() -> int {
-        RMT_TRY(emit_tail(false));
-        if (tail) RMT_HIP(hipStreamWaitEvent(st, S->e_tail, 0));
-        if (tail && tail_p) RMT_HIP(hipStreamWaitEvent(st, S->e_tailp, 0));
-        tail = false;
-        tail_p = false;
-        return RMT_OK;
-    };
-    // the last step's ring record, completed by the next step's k_dt_part (or here)
-    double *ring_e = nullptr;
-    int *const ring_flag = P.shape != RMT_SHAPE_NONE ? S->flag : nullptr;
-    auto flush = [&]() -> int {
-        RMT_TRY(join());
-        if (ring_e) {
-            k_ring_put<<<1, 64, 0, st>>>(sc, ring_flag, ring_e);
-            RMT_LAUNCHED();
-            ring_e = nullptr;
+    }
+    double dv[DIAG_VALS];
+    int fl[4] = {0, 0, 0, 0};   // non-finite, (momentum), fitted, sweep aborted
+    RMT_HIP(hipMemcpyAsync(dv, R.sc + 2, sizeof(dv), hipMemcpyDeviceToHost, st));
+    if (K.solid) RMT_HIP(hipMemcpyAsync(fl, S->flag, sizeof(fl), hipMemcpyDeviceToHost, st));
+    if (S->prof) RMT_HIP(hipEventRecord(S->pev[6], st));
+    RMT_HIP(hipStreamSynchronize(st));
+    if (S->prof) {
+        float f;
+        for (int k = 0; k < 6; ++k) {
+            RMT_HIP(hipEventElapsedTime(&f, S->pev[k], S->pev[k + 1]));
+            S->ms[k] += f; S->calls[k] += 1;
         }
-        if (!slot) return RMT_OK;
-        std::vector<double> h((size_t)slot * RING_VALS);
-        RMT_HIP(hipMemcpyAsync(h.data(), S->ring, h.size() * sizeof(double),
-                               hipMemcpyDeviceToHost, st));
-        RMT_HIP(hipStreamSynchronize(st));
-        const int cnt = slot;
-        slot = 0;
-        for (int k = 0; k < cnt; ++k) {
-            const double *e = h.data() + (size_t)k * RING_VALS;
-            int fl[4];
-            for (int q = 0; q < 4; ++q) fl[q] = (int)e[DIAG_VALS + 2 + q];
-            RMT_TRY(sim_record(S, e, e[DIAG_VALS], e[DIAG_VALS + 1], fl));
+        RMT_HIP(hipEventElapsedTime(&f, S->ctx->ev[0], S->ctx->ev[1]));
+        S->ms[6] += f; S->calls[6] += 4;
+        if (K.solid) {
+            RMT_HIP(hipEventElapsedTime(&f, S->ctx->ev[2], S->ctx->ev[3]));
+            S->ms[7] += f; S->calls[7] += 1;
         }
-        return RMT_OK;
-    };
+    }
+    advance_known_plane(S, R.nb);
+    return sim_record(S, dv, R.hv[0], R.dt, fl);
+}
+
+// run on S->st1 (highest priority) when it exists: ordered after the caller's stream on
+// entry, the caller's stream ordered after it on every return
+struct OnHi {
+    rmt_sim *S; hipStream_t user;
+    ~OnHi() {
+        if (!S->st1) return;
+        (void)hipEventRecord(S->e_out, S->st1);
+        (void)hipStreamWaitEvent(user, S->e_out, 0);
+    }
+};
+// the map buffers swap roles every step; at the call's end the state is copied back into
+// the buffers rmt_sim_field hands out (one copy per call instead of one per step).  Runs
+// on the step's stream before that stream is handed back (destroyed first).
+struct MapHome {
+    rmt_sim *S;
+    ~MapHome() {
+        if (S->X1 == S->X1h) return;
+        const size_t b = (size_t)S->P.ny * S->P.nx * sizeof(double);
+        (void)hipMemcpyAsync(S->X1h, S->X1, b, hipMemcpyDeviceToDevice, S->ctx->stream);
+        (void)hipMemcpyAsync(S->X2h, S->X2, b, hipMemcpyDeviceToDevice, S->ctx->stream);
+        std::swap(S->X1, S->X1n);
+        std::swap(S->X2, S->X2n);
+        S->zcur ^= 1;
+    }
+};
+
+int rmt_sim_step(rmt_sim *S, int nsteps, double t_end) {
+    RMT_CHECK(S, RMT_EINVAL, "null sim");
+    rmt_ctx *ctx = S->ctx;
+    const rmt_sim_params &P = S->P;
+    hipStream_t user = ctx->stream;
+    StreamScope on_st1(ctx, S->st1 ? S->st1 : user);
+    OnHi on_hi{S, user};
+    MapHome map_home{S};
+    if (S->st1) {
+        RMT_HIP(hipEventRecord(S->e_in, user));
+        RMT_HIP(hipStreamWaitEvent(S->st1, S->e_in, 0));
+    }
+    const StepSched K = step_sched(S, t_end);
+    StepRun R;
+    R.st = ctx->stream;
+    hipStream_t st = R.st;
+    R.sc = S->dscr + DIAG_BLOCKS * DIAG_VALS;
+    R.ring_flag = K.solid ? S->flag : nullptr;
     // a carried state (rmt_sim_set_carry): this call's first step uses the geometry, known
     // plane, prep planes and max |u|^2 partials the previous call's last step left
     const bool carry = S->carry_on && S->carry_valid && S->carry_gen == ctx->bytes_gen &&
@@ -1217,435 +1721,41 @@ int rmt_sim_step(rmt_sim *S, int nsteps, double t_end) {
     if (!carry) {
         S->bits_ready = false;   // the caller may have changed the map between calls
         // ... or the prep planes: the first prep of a call writes every segment
-        if (S->pconst) RMT_HIP(hipMemsetAsync(S->pconst, 0, (size_t)ny * (nx / 64), st));
+        if (S->pconst) RMT_HIP(hipMemsetAsync(S->pconst, 0, (size_t)P.ny * (P.nx / 64), st));
     }
-    // the next step's rim words and extrapolation geometry, prepared on the second stream
-    // beside this step's projection (they depend on the known plane alone)
-    const bool geo_env = ctx->opt.early_geometry != 0;
-    // the column pass's transpose of the row blocks without fix-up rows beside the chain
-    // (RMT_EARLY_TRANSPOSE, default on)
-    const bool early_t_env = ctx->opt.early_transpose != 0;
-    bool early_t = false;
-    // k_phi_rebuild writes the momentum's pure-fluid flags (RMT_FUSED_FLUID, default on)
-    const bool fluid_env = ctx->opt.fused_fluid != 0;
-    bool geo_ready = carry;
-    bool m2_last = false;   // the last step's projection wrote the max |u|^2 partials
+    R.geo_ready = carry;
     for (int it = 0; it < nsteps; ++it) {
         if (!(S->t < t_end)) break;
+        const bool more = it + 1 < nsteps;
         if (S->prof) RMT_HIP(hipEventRecord(S->pev[0], st));
-        // 1. dt (compute_timestep + the drivers' clip to t_end); NaN-propagating max so it
-        // also bounds the velocities for the SL block skip
-        double hv[2] = {0.0, 0.0}, dt = NAN;
-        if (async && (it > 0 || m2_ok)) {
-            k_dt_part<<<DTP_BLOCKS, 256, 0, st>>>(S->m2part, S->m2n, S->dt_const, P.cfl, P.dx,
-                                                  sc, S->m2acc, ring_e ? ring_flag : nullptr,
-                                                  ring_e);
-            RMT_LAUNCHED();
-            ring_e = nullptr;
-        } else {
-            RMT_CHECK(!ring_e, RMT_EINVAL, "sim: ring record pending on a synchronous step");
-            RMT_TRY(reduce_maxsq2_nan(ctx, S->u, S->v, n, sc));
-            k_dt<<<1, 1, 0, st>>>(sc, S->dt_const, P.cfl, P.dx, sc + 1);
-            RMT_LAUNCHED();
-        }
-        if (!async) {
-            RMT_HIP(hipMemcpyAsync(hv, sc, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-            RMT_HIP(hipStreamSynchronize(st));
-            dt = hv[1];
-            if (S->t + dt > t_end) dt = t_end - S->t;
-        }
-        const double *dtp = async ? sc + 1 : nullptr;
-        const bool solid = P.shape != RMT_SHAPE_NONE;
-        // this step's phi kernels also write the next step's known plane (split advection)
-        unsigned long long *nb = (solid && P.scheme == RMT_SCHEME_SEMILAGRANGIAN && S->e_bits &&
-                                  nx % 64 == 0) ? S->kbits_next : nullptr;
-        rmt_momentum_params M{};
-        M.bc_kind = P.bc_kind; M.lid = P.lid; M.mu_s = P.mu_s; M.kappa = P.kappa;
-        M.eta_s = P.eta_s; M.rho_s = P.rho_s; M.rho_f = P.rho_f; M.mu_f = P.mu_f; M.w_t = P.w_t;
-        M.dx = P.dx; M.dy = P.dy; M.dt = dt; M.stress_band = P.stress_band;
-        M.detg_clamp = P.detg_clamp;
-        MomWork W = mom_work(S->mw, n, S->mbytes, S->flag + 1);
-        W.dtp = dtp;
-        W.prep_const = S->pconst;
-        // the extrapolation chain occupies one CU for milliseconds; everything it does not
-        // feed runs beside it: the momentum of every cell, from the pre-extrapolation map, on
-        // a second stream, re-run afterwards on the tiles within reach of a target
-        const bool no_overlap = ctx->opt.no_overlap != 0;
-        const bool side_tail = ctx->opt.side_tail != 0;
-        // the parallel extrapolation: its values pass (~0.5 ms at N=4096, mostly the
-        // one-workgroup combine) runs beside the speculative momentum too (RMT_PAR_OVERLAP=0:
-        // in order, the momentum after it)
-        const bool par = extrap_par_enabled();
-        const bool par_ov = ctx->opt.par_overlap != 0;
-        const bool overlap = solid && S->st2 && !no_overlap && (!par || par_ov);
-        bool fixprep = false;   // the fused fix-up prep (set where the extrapolation runs)
-        bool seg_diag = false;  // this step's fbits and fix-up tile marks are set (k_diag_seg)
+        RMT_TRY(step_dt(S, K, R, it > 0 || m2_ok, t_end));
         if (S->prof) RMT_HIP(hipEventRecord(S->pev[1], st));
-        if (solid) {
-            // (the output buffer's zero-tile flags hold only when the flagged pass writes it;
-            // the flagged pass reads them first: the rim pass and the chain below write only rim
-            // cells, and a tile with a rim cell never uses them)
-            const bool zo_valid = S->zv[S->zcur ^ 1];
-            S->zv[S->zcur ^ 1] = false;
-            // 2. advect the reference map with the pre-advection level set and mask
-            // (on the asynchronous path the previous step's ring record -- k_dt_part or k_ring_put --
-            // cleared it)
-            if (!(async && it > 0)) RMT_HIP(hipMemsetAsync(S->flag, 0, sizeof(int), st));
-            if (P.scheme == RMT_SCHEME_SEMILAGRANGIAN && overlap && S->e_bits) {
-                // known plane -> rim words -> the rim's advection here; the rest on the second
-                // stream, beside the extrapolation (which reads rim cells only)
-                const dim3 gsl((nx + 255) / 256, ny);
-                if (!S->bits_ready) {
-                    k_sim_bits<<<gsl, 256, 0, st>>>(S->X1, S->X2, nx, P.x0, P.y0, P.R, S->kbits);
-                    RMT_LAUNCHED();
-                }
-                const long nseg = (long)ny * ((nx + 255) / 256);
-                int *scount = S->segs + nseg;
-                if (geo_ready) {
-                    RMT_HIP(hipStreamWaitEvent(st, S->e_geo, 0));
-                } else {
-                    RMT_TRY(rim_words(ctx, S->kbits, ny, nx, (nx + 63) / 64, S->rimw, S->rimcnt));
-                    RMT_HIP(hipMemsetAsync(scount, 0, sizeof(int), st));
-                    k_rim_segments<<<grid1d(nseg, 256), 256, 0, st>>>(S->rimw, ny, nx, S->segs,
-                                                                       scount);
-                }
-                k_sim_sl_rim<<<4096, 256, 0, st>>>(   // ~one rim segment per block
-                    S->X1, S->X2, S->u, S->v, S->xs, S->ys, ny, nx, dt, divk_make(P.dx), divk_make(P.dy), P.x0, P.y0,
-                    P.R, S->X1n, S->X2n, S->flag, sc, dtp, S->rimw, S->segs, scount);
-            } else if (P.scheme == RMT_SCHEME_SEMILAGRANGIAN) {
-                k_sim_sl_t<0><<<dim3((nx + SLT_X - 1) / SLT_X, (ny + SLT_Y - 1) / SLT_Y), SLT_X * SLT_Y,
-                             0, st>>>(S->X1, S->X2, S->u, S->v, S->xs, S->ys, ny, nx, dt,
-                                      divk_make(P.dx), divk_make(P.dy), P.x0, P.y0, P.R, S->X1n,
-                                      S->X2n, S->phi_pre, S->flag, S->kbits, sc, dtp, 0, nullptr);
-            } else if (P.scheme == RMT_SCHEME_SEMILAGRANGIAN_CUBIC) {
-                k_sim_sl_cubic<<<g, 256, 0, st>>>(S->X1, S->X2, S->u, S->v, S->xs, S->ys, ny, nx,
-                                                  dt, P.dx, P.dy, P.x0, P.y0, P.R, S->X1n,
-                                                  S->X2n, S->phi_pre, S->flag);
-            } else {
-                // Eulerian schemes on the pre-advection level set, w_cut = 0 as the drivers
-                k_sim_phi_mask<<<g, 256, 0, st>>>(S->X1, S->X2, S->u, S->v, n, P.x0, P.y0, P.R,
-                                                  S->phi_pre, S->flag);
-                for (int comp = 0; comp < 2; ++comp) {
-                    const double *q = comp ? S->X2 : S->X1;
-                    double *o = comp ? S->X2n : S->X1n;
-                    if (P.scheme == RMT_SCHEME_WENO5)
-                        RMT_TRY(rmt_advect_weno5_rk3(ctx, q, S->u, S->v, P.dx, P.dy, dt,
-                                                     S->phi_pre, 0.0, o));
-                    else
-                        RMT_TRY(rmt_advect_central_rk3(ctx, q, S->u, S->v, P.dx, P.dy, dt,
-                                                       S->phi_pre, 0.0,
-                                                       P.scheme == RMT_SCHEME_CONSERVATIVE, o));
-                }
-                k_mask_mul<<<g, 256, 0, st>>>(S->X1n, S->X2n, S->phi_pre, n);
-            }
-            RMT_LAUNCHED();
+        if (K.solid) {
+            RMT_TRY(step_advect(S, K, R, it == 0));
             if (S->prof) RMT_HIP(hipEventRecord(S->pev[2], st));
-            // 3. narrow-band extrapolation (exact raster-order semantics), in place; with the
-            // overlap, the speculative phi + momentum start on the second stream once the
-            // chip-wide passes are done and the one-workgroup chain kernel is launched
-            if (overlap) ctx->ev_chain = S->e_sl;
-            const bool kb = P.scheme == RMT_SCHEME_SEMILAGRANGIAN;   // k_sim_sl wrote kbits
-            if (geo_ready && !overlap) RMT_HIP(hipStreamWaitEvent(st, S->e_geo, 0));
-            // with the fused fix-up prep (below) the status words are copied by its kernel
-            const bool fp_env = ctx->opt.fused_fixprep != 0;
-            fixprep = overlap && fp_env && P.shape == RMT_SHAPE_DISC && nx % 64 == 0 &&
-                      momentum_mode() != 2 && P.layers > 0;
-            int *dstat = fixprep ? nullptr : S->flag + 2;
-            // with the fused fix-up prep the fallback sweep runs on the second stream beside the
-            // chain (the fix-up joins that stream before it reads the map or the status)
-            ctx->ex_sweep_defer = fixprep;
-            ctx->ev_chain_vals = fixprep;   // ev_chain completes with the values pass
-            const int es = geo_ready && P.layers > 0
-                               ? extrap_finish(ctx, P.dx, P.dy, P.layers, S->X1n, S->X2n, dstat)
-                               : extrapolate(ctx, S->X1n, S->X2n, S->phi_pre, P.dx, P.dy, P.layers,
-                                             S->X1n, S->X2n, dstat, kb ? S->kbits : nullptr);
-            geo_ready = false;
-            ctx->ev_chain = nullptr;
-            ctx->ex_sweep_defer = false;
-            ctx->ev_chain_vals = false;
-            RMT_TRY(es);
-            if (overlap) {
-                RMT_HIP(hipStreamWaitEvent(S->st2, S->e_sl, 0));
-                const int dly_side = ctx->opt.test_delay_side;
-                if (dly_side) { k_delay<<<1, 1, 0, S->st2>>>(dly_side); RMT_LAUNCHED(); }
-                if (fixprep && ctx->ex_chain && !ctx->ex_par)
-                    RMT_TRY(extrap_sweep(ctx, P.dx, P.dy, P.layers, S->X1n, S->X2n, S->st2));
-                // the previous step's tail, beside the chain (e_sl, recorded by this step's
-                // extrapolation when it has layers, follows that step's projection)
-                RMT_TRY(emit_tail(P.layers > 0));
-                // the fix-up tiles and the rows they reach depend on the known plane only
-                ctx->stream = S->st2;
-                const int fs = extrap_fix_tiles(ctx, P.layers, 12, S->tiles, S->tcount);
-                ctx->stream = st;
-                RMT_TRY(fs);
-                const bool tm = ctx->opt.diag_seg != 0;
-                if (S->split_proj) {
-                    RMT_HIP(hipMemsetAsync(S->rowmark, 0, ny, S->st2));
-                    if (tm) RMT_HIP(hipMemsetAsync(S->tmark, 0, S->max_tiles, S->st2));
-                    k_mark_rows<<<list_grid(S->max_tiles), 64, 0, S->st2>>>(
-                        S->tiles, S->tcount, (nx + MOM_TX - 1) / MOM_TX, ny, S->rowmark,
-                        tm ? S->tmark : nullptr);
-                    RMT_LAUNCHED();
-                }
-                MomWork Wf = W;
-                if (tail_p) Wf.wait_p = S->e_tailp;   // (emit_tail above: p on another stream)
-                const bool fl_ok = fluid_env && P.shape == RMT_SHAPE_DISC && nx % 64 == 0 &&
-                                   MOM_TX == 64;
-                // the SL pass also leaves phi, the known-plane words and per-tile fluid bits
-                // (RMT_SL_PHI, default on): k_phi_rebuild_fluid's outputs without its pass
-                const bool sl_phi = P.scheme == RMT_SCHEME_SEMILAGRANGIAN && S->e_bits &&
-                                    fl_ok && ctx->opt.sl_phi;
-                if (P.scheme == RMT_SCHEME_SEMILAGRANGIAN && S->e_bits) {
-                    // the advection of every non-rim cell, once the chain has started (earlier
-                    // its blocks would crowd out the one-workgroup band passes); with the
-                    // zero-tile flags (sl_zero_flags, with sl_phi) the tiles that stay +0.0 move
-                    // no map or phi bytes
-                    const bool zon = sl_phi && S->zf[0] && ctx->opt.sl_zero_flags;
-                    const int zi = S->zcur, zo = S->zcur ^ 1;
-                    k_sim_sl_t<0><<<dim3((nx + SLT_X - 1) / SLT_X, (ny + SLT_Y - 1) / SLT_Y),
-                                 SLT_X * SLT_Y, 0, S->st2>>>(
-                        S->X1, S->X2, S->u, S->v, S->xs, S->ys, ny, nx, dt, divk_make(P.dx),
-                        divk_make(P.dy), P.x0, P.y0, P.R, S->X1n, S->X2n, S->phi_pre, S->flag,
-                        nullptr, sc, dtp, 2, S->rimw, sl_phi ? S->phi : nullptr,
-                        fluid_threshold(&M), sl_phi ? fluid_bits_buf(W) : nullptr,
-                        sl_phi ? nb : nullptr, 0, 0, zon && S->zv[zi] ? S->zf[zi] : nullptr,
-                        zon ? S->zf[zo] : nullptr, zon && zo_valid);
-                    RMT_LAUNCHED();
-                    S->zv[zo] = zon;
-                }
-                seg_diag = sl_phi && S->split_proj && tm && !P.energies;
-                if (sl_phi) {
-                    Wf.fluid_bits = fluid_bits_buf(W);
-                } else if (fl_ok) {
-                    // phi and the stage kernels' pure-fluid flags in one pass
-                    k_phi_rebuild_fluid<<<g, 256, 0, S->st2>>>(
-                        S->X1n, S->X2n, n, nx, (nx + 63) / 64, P.x0, P.y0, P.R, S->phi, nullptr,
-                        nullptr, nb, fluid_threshold(&M), fluid_rows_buf(W, 0, nx));
-                    Wf.fluid_rows_ready = true;
-                    RMT_LAUNCHED();
-                } else {
-                    k_phi_rebuild<<<g, 256, 0, S->st2>>>(S->X1n, S->X2n, n, P.shape, P.x0, P.y0,
-                                                          P.R, S->phi, nullptr, nullptr, nb);
-                    RMT_LAUNCHED();
-                }
-                ctx->stream = S->st2;
-                int ms = momentum_rk4(ctx, &M, S->u, S->v, S->p, S->X1n, S->X2n, S->phi,
-                                      S->us, S->vs, S->sxx, S->sxy, S->syy, S->J, Wf);
-                if (ms == RMT_OK) ms = hipEventRecord(S->e_mom, S->st2) ? RMT_EDEVICE : RMT_OK;
-                // and the projection's rows from the speculative u*, v* (the fix-up tiles the
-                // main stream re-runs meanwhile only feed rows it redoes afterwards)
-                if (ms == RMT_OK && S->split_proj)
-                    ms = projection_rows(ctx, S->us, S->vs, P.dx, P.dy, dtp, dt, P.rho_f, S->p,
-                                         nullptr, nullptr, nullptr, 0,
-                                         ctx->opt.skip_marked_rows ? S->rowmark : nullptr);
-                // and the row blocks no fix-up row falls in, transposed for the column pass
-                if (ms == RMT_OK && S->split_proj && early_t_env) {
-                    ms = dct_transpose_unmarked(ctx, ctx->scratch + n, S->rowmark);
-                    early_t = ms == RMT_OK;
-                }
-                ctx->stream = st;
-                RMT_TRY(ms);
-                RMT_HIP(hipEventRecord(S->e_rows, S->st2));
-            }
-            if (S->prof) RMT_HIP(hipEventRecord(S->pev[3], st));
+            RMT_TRY(step_extrapolate(S, K, R));
+            if (K.overlap) RMT_TRY(step_side_stream(S, K, R));
             // the flags (non-finite velocity, sweep aborted) are read with the diagnostics at
             // the end of the step: no host round trip between the chain and the projection
-        }
-        if (S->prof && !solid) {
+        } else if (S->prof) {
             RMT_HIP(hipEventRecord(S->pev[2], st));
-            RMT_HIP(hipEventRecord(S->pev[3], st));
         }
-        // one join of the second stream instead of two (RMT_MERGED_JOIN, default on; not in
-        // the parallel mode, whose values pass ends long before that stream's row passes):
-        // e_rows, after the speculative momentum AND the projection's rows, here -- beside the
-        // ~3 ms chain both are done -- and no second wait before the projection
-        const bool mj_env = ctx->opt.merged_join != 0;
-        const bool mjoin = overlap && mj_env && !par;
-        if (overlap) {
-            const int dly_main = ctx->opt.test_delay_main;
-            if (dly_main) { k_delay<<<1, 1, 0, st>>>(dly_main); RMT_LAUNCHED(); }
-            // 4 + 5 on the tiles the extrapolation can reach
-            RMT_HIP(hipStreamWaitEvent(st, mjoin ? S->e_rows : S->e_mom, 0));
-            const int tiles_x = (nx + MOM_TX - 1) / MOM_TX;
-            // phi on the tiles and the momentum's prep there in one kernel (RMT_FUSED_FIXPREP,
-            // default on where nx % 64 == 0), which also copies the extrapolation's status
-            // the next step's geometry below starts once the known plane is final (e_kb)
-            const bool geo_next = async && geo_env && nb && P.layers > 0 &&
-                                  (it + 1 < nsteps || S->carry_on);
-            if (fixprep) {
-                RMT_TRY(fixup_phi_prep(ctx, &M, W, S->X1n, S->X2n, P.x0, P.y0, P.R, nullptr, nullptr,
-                                       S->phi, nb, S->sxx, S->sxy, S->syy, S->J, S->tiles,
-                                       S->tcount, S->max_tiles, extrap_status(ctx, P.layers),
-                                       S->flag + 2, geo_next ? S->e_kb : nullptr));
-            } else {
-                k_phi_tiles<<<list_grid(S->max_tiles), 256, 0, st>>>(S->X1n, S->X2n, ny, nx, P.x0, P.y0, P.R,
-                                                           S->phi, nullptr, nullptr, S->tiles, S->tcount,
-                                                           tiles_x, nb);
-                RMT_LAUNCHED();
-            }
-            if (geo_next) {
-                // the next step's known plane is final (the phi kernel above): its rim words, rim
-                // segments and extrapolation geometry on the second stream, beside the rest of
-                // this step (nothing there uses them or the extrapolation workspace).  Issued
-                // before the fix-up stages: after them its few-block kernels would share the CUs
-                // with the projection's FFT passes (measured: the step no faster)
-                hipStream_t sg = S->st2;
-                if (!fixprep) RMT_HIP(hipEventRecord(S->e_kb, st));   // (else: with the prep)
-                RMT_HIP(hipStreamWaitEvent(sg, S->e_kb, 0));
-                // this step's diagnostics (phi, J: final after the fix-up prep) on the second
-                // stream, beside the projection, instead of in the tail beside the next chain;
-                // they land in the ring slot this step's record takes below.  diag_first: ahead
-                // of the geometry, beside the latency-bound fix-up stages (behind it they
-                // overlapped the projection's DCT passes)
-                // J is final here only with the fused fix-up prep (it writes J and records e_kb
-                // on completion); without it momentum_fixup's prep writes J on the main stream
-                // later, so the diagnostics stay in the tail
-                const bool early_diag = fixprep && side_tail && S->split_proj && !P.energies;
-                auto diag_now = [&]() {
-                    DiagArgs D{S->phi, S->J, S->xs, S->ys, S->u, S->v, S->X1n, S->X2n, ny, nx,
-                               P.energies, P.dx, P.dy, P.w_t, P.rho_s, P.rho_f, P.mu_f, P.eta_s,
-                               P.mu_s, P.kappa, 0, ny};
-                    if (seg_diag) { D.fbits = fluid_bits_buf(W); D.tmark = S->tmark; }
-                    diag_partials(D, S->dscr, sg, ctx->opt.diag_seg != 0);
-                    k_diag_p2<<<1, DIAG_T, 0, sg>>>(S->dscr, S->ring + (size_t)slot * RING_VALS);
-                    diag_early = true;
-                };
-                if (early_diag && ctx->opt.diag_first) { diag_now(); RMT_LAUNCHED(); }
-                const long nseg = (long)ny * ((nx + 255) / 256);
-                int *scount = S->segs + nseg;
-                ctx->stream = sg;
-                int gs = rim_words(ctx, nb, ny, nx, (nx + 63) / 64, S->rimw, S->rimcnt);
-                if (gs == RMT_OK)
-                    gs = hipMemsetAsync(scount, 0, sizeof(int), sg) ? RMT_EDEVICE : RMT_OK;
-                if (gs == RMT_OK) {
-                    k_rim_segments<<<grid1d(nseg, 256), 256, 0, sg>>>(S->rimw, ny, nx,
-                                                                       S->segs, scount);
-                    gs = extrap_geometry(ctx, S->X1n, S->X2n, nullptr, P.dx, P.dy, P.layers,
-                                         S->X1n, S->X2n, nb);
-                }
-                ctx->stream = st;
-                RMT_TRY(gs);
-                RMT_HIP(hipEventRecord(S->e_geo, sg));
-                geo_ready = true;
-                if (early_diag && !ctx->opt.diag_first) { diag_now(); RMT_LAUNCHED(); }
-            }
-            RMT_TRY(momentum_fixup(ctx, &M, S->u, S->v, S->p, S->X1n, S->X2n, S->phi, S->us, S->vs,
-                                   S->sxx, S->sxy, S->syy, S->J, W, S->tiles, S->tcount,
-                                   S->max_tiles, nullptr, fixprep));
-        } else {
-            // 4. phi from the advected + extrapolated map (and the momentum's pure-fluid flags)
-            if (fluid_env && P.shape == RMT_SHAPE_DISC && nx % 64 == 0 && MOM_TX == 64) {
-                k_phi_rebuild_fluid<<<g, 256, 0, st>>>(
-                    S->X1n, S->X2n, n, nx, (nx + 63) / 64, P.x0, P.y0, P.R, S->phi, nullptr,
-                    nullptr, nb, fluid_threshold(&M), fluid_rows_buf(W, 0, nx));
-                W.fluid_rows_ready = true;
-            } else {
-                k_phi_rebuild<<<g, 256, 0, st>>>(S->X1n, S->X2n, n, P.shape, P.x0, P.y0, P.R,
-                                                  S->phi, nullptr, nullptr, nb);
-            }
-            RMT_LAUNCHED();
-            if (par && async && geo_env && nb && P.layers > 0 && S->st2 && it + 1 < nsteps) {
-                // the next step's extrapolation geometry (known plane nb) beside this step's
-                // momentum and projection
-                RMT_HIP(hipEventRecord(S->e_kb, st));
-                RMT_HIP(hipStreamWaitEvent(S->st2, S->e_kb, 0));
-                ctx->stream = S->st2;
-                const int gs = extrap_geometry(ctx, S->X1n, S->X2n, nullptr, P.dx, P.dy,
-                                               P.layers, S->X1n, S->X2n, nb);
-                ctx->stream = st;
-                RMT_TRY(gs);
-                RMT_HIP(hipEventRecord(S->e_geo, S->st2));
-                geo_ready = true;
-            }
-            // 5. momentum (RK4)
-            RMT_TRY(momentum_rk4(ctx, &M, S->u, S->v, S->p, S->X1n, S->X2n, S->phi, S->us, S->vs,
-                                 S->sxx, S->sxy, S->syy, S->J, W));
-        }
-        if (S->prof) RMT_HIP(hipEventRecord(S->pev[4], st));
-        // 6. projection (constant density rho_f; Neumann DCT-I)
-        if (overlap && S->split_proj) {
-            // redo the rhs on the fix-up tiles (+1 cell) and the row DCT of the rows they
-            // reach, then the column pass and the rest
-            if (!mjoin) RMT_HIP(hipStreamWaitEvent(st, S->e_rows, 0));
-            RMT_TRY(projection_rows(ctx, S->us, S->vs, P.dx, P.dy, dtp, dt, P.rho_f, S->p,
-                                    S->rowmark, S->tiles, S->tcount, S->max_tiles));
-            RMT_TRY(projection_finish(ctx, S->us, S->vs, P.dx, P.dy, dtp, dt, P.rho_f, P.bc_kind,
-                                      P.lid, S->p, S->u, S->v, S->p,
-                                      async ? S->m2part : nullptr, !(async && side_tail),
-                                      early_t ? S->rowmark : nullptr));
-            early_t = false;
-        } else if (async)
-            RMT_TRY(projection_dev(ctx, S->us, S->vs, P.dx, P.dy, dtp, P.rho_f, P.bc_kind, P.lid,
-                                   S->p, S->u, S->v, S->p, S->m2part));
+        if (S->prof) RMT_HIP(hipEventRecord(S->pev[3], st));
+        if (K.overlap)
+            RMT_TRY(step_fixup(S, K, R, more || S->carry_on));
         else
-            RMT_TRY(rmt_pressure_projection(ctx, S->us, S->vs, P.dx, P.dy, dt, P.rho_f,
-                                            P.bc_kind, P.lid, S->p, S->u, S->v, S->p));
+            RMT_TRY(step_inorder(S, K, R, more));
+        if (S->prof) RMT_HIP(hipEventRecord(S->pev[4], st));
+        RMT_TRY(step_project(S, K, R));
         if (S->prof) RMT_HIP(hipEventRecord(S->pev[5], st));
-        m2_last = async;
-        // the advected + extrapolated map (X1n, X2n) is the state from here on: the two map
-        // buffers swap roles instead of copying the map back (restored at the call's end)
-        std::swap(S->X1, S->X1n);
-        std::swap(S->X2, S->X2n);
-        S->zcur ^= 1;
-        // 7. diagnostics (running them beside the projection on the second stream measured
-        // no gain: both are HBM-bound)
-        DiagArgs D{S->phi, S->J, S->xs, S->ys, S->u, S->v, S->X1, S->X2, ny, nx, P.energies,
-                   P.dx, P.dy, P.w_t, P.rho_s, P.rho_f, P.mu_f, P.eta_s, P.mu_s, P.kappa, 0, ny};
-        if (async && overlap && S->split_proj && side_tail) {
-            // p -= mean(p) and the diagnostics on the second stream: nothing before the next
-            // step's chain reads p or writes what they read (that stream's next work -- the
-            // speculative phi, momentum -- is queued behind them)
-            double *e = S->ring + (size_t)slot * RING_VALS;
-            pend_e = e;
-            pending = true;
-            pend_seg = seg_diag;
-            pend_diag_done = diag_early;
-            diag_early = false;
-            ring_e = e;
-            if (nb) { std::swap(S->kbits, S->kbits_next); S->bits_ready = true; }
-            if (++slot == S->sync_every) RMT_TRY(flush());
-            continue;
-        }
-        diag_partials(D, S->dscr, st, ctx->opt.diag_seg != 0);
-        if (async) {
-            double *e = S->ring + (size_t)slot * RING_VALS;
-            k_diag_p2<<<1, DIAG_T, 0, st>>>(S->dscr, e);
-            RMT_LAUNCHED();
-            ring_e = e;
-            if (nb) { std::swap(S->kbits, S->kbits_next); S->bits_ready = true; }
-            if (++slot == S->sync_every) RMT_TRY(flush());
-            continue;
-        }
-        k_diag_p2<<<1, DIAG_T, 0, st>>>(S->dscr, sc + 2);
-        RMT_LAUNCHED();
-        double dv[DIAG_VALS];
-        int fl[4] = {0, 0, 0, 0};   // non-finite, (momentum), fitted, sweep aborted
-        RMT_HIP(hipMemcpyAsync(dv, sc + 2, sizeof(dv), hipMemcpyDeviceToHost, st));
-        if (solid) RMT_HIP(hipMemcpyAsync(fl, S->flag, sizeof(fl), hipMemcpyDeviceToHost, st));
-        if (S->prof) RMT_HIP(hipEventRecord(S->pev[6], st));
-        RMT_HIP(hipStreamSynchronize(st));
-        if (S->prof) {
-            float f;
-            for (int k = 0; k < 6; ++k) {
-                RMT_HIP(hipEventElapsedTime(&f, S->pev[k], S->pev[k + 1]));
-                S->ms[k] += f; S->calls[k] += 1;
-            }
-            RMT_HIP(hipEventElapsedTime(&f, ctx->ev[0], ctx->ev[1]));
-            S->ms[6] += f; S->calls[6] += 4;
-            if (solid) {
-                RMT_HIP(hipEventElapsedTime(&f, ctx->ev[2], ctx->ev[3]));
-                S->ms[7] += f; S->calls[7] += 1;
-            }
-        }
-        if (nb) { std::swap(S->kbits, S->kbits_next); S->bits_ready = true; }
-        RMT_TRY(sim_record(S, dv, hv[0], dt, fl));
+        RMT_TRY(step_record(S, K, R));
     }
     // the geometry prepared for a next call is joined here: nothing of this call stays in
     // flight on the second stream (the caller may reuse the context's workspace)
-    if (geo_ready) RMT_HIP(hipStreamWaitEvent(st, S->e_geo, 0));
-    RMT_TRY(flush());
-    S->carry_valid = S->carry_on && geo_ready;
-    S->m2_valid = m2_last;
+    if (R.geo_ready) RMT_HIP(hipStreamWaitEvent(st, S->e_geo, 0));
+    RMT_TRY(flush(S, K, R));
+    S->carry_valid = S->carry_on && R.geo_ready;
+    S->m2_valid = R.m2_last;
     S->carry_gen = ctx->bytes_gen;
     S->carry_cfg = extrap_config_gen();
     return RMT_OK;

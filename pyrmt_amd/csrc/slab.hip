@@ -415,7 +415,8 @@ int rim_words(rmt_ctx *ctx, const u64 *bits, int ny, int nx, int W, u64 *rimw, i
 int slab_rim_extrapolate(rmt_ctx *ctx, const double *gathered, const long long *counts, int G,
                          long long cap, double *X1d, double *X2d, const u64 *bits, double dx,
                          double dy, int layers, int *exflags, double *X1n, double *X2n,
-                         long c_lo, long c_hi, const double *gs, hipEvent_t geo) {
+                         long c_lo, long c_hi, const double *gs, hipEvent_t geo,
+                         const ExtrapCall &call) {
     Counts cn{};
     for (int k = 0; k < G && !gs; ++k) {
         RMT_CHECK(counts[k] >= 0 && counts[k] <= cap, RMT_EINVAL, "slab: rim count > cap");
@@ -428,9 +429,10 @@ int slab_rim_extrapolate(rmt_ctx *ctx, const double *gathered, const long long *
     }
     if (geo && layers > 0) {   // the geometry ran beside the previous step's projection
         RMT_HIP(hipStreamWaitEvent(ctx->stream, geo, 0));
-        RMT_TRY(extrap_finish(ctx, dx, dy, layers, X1d, X2d, exflags));
+        RMT_TRY(extrap_finish(ctx, dx, dy, layers, X1d, X2d, exflags, call));
     } else {
-        RMT_TRY(extrapolate(ctx, X1d, X2d, nullptr, dx, dy, layers, X1d, X2d, exflags, bits));
+        RMT_TRY(extrapolate(ctx, X1d, X2d, nullptr, dx, dy, layers, X1d, X2d, exflags, bits,
+                            call));
     }
     if (tot > 0) {
         k_rim_writeback<<<grid1d(tot, 256), 256, 0, ctx->stream>>>(gathered, cn, G, cap, X1d, X2d,
@@ -695,18 +697,14 @@ int rmt_slab_geometry(rmt_slab *S) {
     if (P.layers <= 0) return RMT_OK;
     RMT_HIP(hipEventRecord(S->e_bits, ctx->stream));
     RMT_HIP(hipStreamWaitEvent(S->st2, S->e_bits, 0));
-    hipStream_t st = ctx->stream;
-    ctx->stream = S->st2;
     // (test switch: the geometry starts late, so that a dropped one overlaps what follows)
     if (ctx->opt.test_delay_geo) { k_slab_delay<<<1, 1, 0, S->st2>>>(ctx->opt.test_delay_geo); RMT_LAUNCHED(); }
-    int gs;
     {
+        StreamScope sc(ctx, S->st2);
         SlabWs ws(S);
-        gs = extrap_geometry(ctx, S->X1d, S->X2d, nullptr, P.dx, P.dy, P.layers, S->X1d, S->X2d,
-                             S->bits_next);
+        RMT_TRY(extrap_geometry(ctx, S->X1d, S->X2d, nullptr, P.dx, P.dy, P.layers, S->X1d,
+                                S->X2d, S->bits_next));
     }
-    ctx->stream = st;
-    RMT_TRY(gs);
     RMT_HIP(hipEventRecord(S->e_geo, S->st2));
     S->geo_ready = true;
     return RMT_OK;
@@ -751,7 +749,8 @@ static int slab_extrapolate(rmt_slab *S, const double *gathered, const long long
     const rmt_sim_params &P = S->P;
     S->spec = S->st2 && !ctx->opt.no_overlap;
     const int jb = std::max(0, S->r0 - 10), je = std::min(S->NY, S->r1 + 10);
-    if (S->spec) ctx->ev_chain = S->e_chain;
+    ExtrapCall ec;
+    if (S->spec) ec.chain_event = S->e_chain;
     const bool geo = S->geo_ready;
     S->geo_ready = false;
     int es;
@@ -760,9 +759,8 @@ static int slab_extrapolate(rmt_slab *S, const double *gathered, const long long
         es = slab_rim_extrapolate(ctx, gathered, counts, S->G, cap, S->X1d, S->X2d, S->bits,
                                   P.dx, P.dy, P.layers, S->flags + 4, S->gv(S->X1n),
                                   S->gv(S->X2n), (long)S->lo * S->NX, (long)S->hi * S->NX, gs,
-                                  geo ? S->e_geo : nullptr);
+                                  geo ? S->e_geo : nullptr, ec);
     }
-    ctx->ev_chain = nullptr;
     if (es != RMT_OK) { S->spec = false; return es; }
     if (!S->spec) {
         k_slab_phi<<<grid1d((long)(je - jb) * S->NX, 256), 256, 0, ctx->stream>>>(
@@ -778,11 +776,10 @@ static int slab_extrapolate(rmt_slab *S, const double *gathered, const long long
         S->gv(S->X1n), S->gv(S->X2n), P.x0, P.y0, P.R, S->NX, jb, je, S->gv(S->phi),
         S->gv(S->X1), S->gv(S->X2));
     RMT_LAUNCHED();
-    hipStream_t st = ctx->stream;
-    ctx->stream = S->st2;
-    const int ms = slab_momentum_pass(S, S->dt_cur, false);
-    ctx->stream = st;
-    RMT_TRY(ms);
+    {
+        StreamScope sc(ctx, S->st2);
+        RMT_TRY(slab_momentum_pass(S, S->dt_cur, false));
+    }
     RMT_HIP(hipEventRecord(S->e_mom, S->st2));
     SlabWs ws(S);   // the tiles come from this step's extrapolation workspace
     return extrap_fix_tiles(ctx, P.layers, 12, S->tiles, S->tcount);

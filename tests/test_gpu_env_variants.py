@@ -62,14 +62,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = ("u", "v", "p", "X1", "X2", "phi", "J")
 
 
-def _run(options=None, ex_mode=None):
+def _run(options=None, ex_mode=None, n=256, steps=12):
     from pyrmt_amd.simulation import soft_disc_in_lid_driven
     from pyrmt_amd.functions import extrapolation_mode
     if ex_mode is not None:
         extrapolation_mode(ex_mode)
     try:
-        s = soft_disc_in_lid_driven(256, options=options)
-        s.step(12)
+        s = soft_disc_in_lid_driven(n, options=options)
+        s.step(steps)
         out = {f: s.get(f) for f in FIELDS}
         out.update({"d_" + k: np.asarray(v) for k, v in s.diagnostics().items()})
     finally:
@@ -109,6 +109,20 @@ def test_schedule_switch_is_bit_identical(default_run, opts):
 @pytest.mark.parametrize("opts", [None, {"fused_fixprep": 0}], ids=["fixprep", "no_fixprep"])
 def test_forced_fallback_sweep_is_bit_identical(default_run, opts):
     _same(_run(opts, ex_mode=2), default_run)
+
+
+@pytest.fixture(scope="module")
+def default_run_196(gpu):
+    return _run(n=196, steps=8)
+
+
+@pytest.mark.parametrize("opts", [{"no_overlap": 1}, {"sim_sync": 1}],
+                         ids=lambda e: ",".join(f"{k}={v}" for k, v in e.items()))
+def test_fallback_branches_are_bit_identical(default_run_196, opts):
+    """N=196: 196 % 64 != 0, so the step has no fluid bits, no fused fix-up prep, no prep
+    skip flags and no zero-tile flags (the branches the N=256 runs above never enter), while
+    195 = 3 5 13 keeps the LDS DCT plan and with it the split projection."""
+    _same(_run(opts, n=196, steps=8), default_run_196)
 
 
 def test_diag_seg_switch(default_run):
