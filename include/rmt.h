@@ -177,12 +177,45 @@ typedef struct {
     double detg_clamp;
 } rmt_momentum_params;
 
-/* functions.py:673-762 momentum_step_rk4 (gamma = 0: surface tension is outside the
- * path).  Outputs u*, v* and the elastic sxx, sxy, syy, J it precomputes. */
+/* functions.py:673-762 momentum_step_rk4 at gamma = 0 (the tuned path; surface tension:
+ * rmt_momentum_step_rk4_st).  Outputs u*, v* and the elastic sxx, sxy, syy, J it precomputes. */
 int rmt_momentum_step_rk4(rmt_ctx *ctx, const rmt_momentum_params *prm, const double *u,
                           const double *v, const double *p, const double *X1, const double *X2,
                           const double *phi, double *u_new, double *v_new, double *sxx,
                           double *sxy, double *syy, double *J);
+/* functions.py:837-861 compute_curvature: div(grad phi / (|grad phi| + 1e-12)) */
+int rmt_compute_curvature(rmt_ctx *ctx, const double *phi, double dx, double dy, double *kappa);
+/* functions.py:864-895 compute_contact_force: the repulsion between two solids around the
+ * mid-surface phi12 = (phi1 - phi2) / 2, cosine window of half-width w_c */
+int rmt_compute_contact_force(rmt_ctx *ctx, const double *phi1, const double *phi2, double k_rep,
+                              double w_c, double dx, double dy, double *fx, double *fy);
+/* functions.py:673-762 momentum_step_rk4 with the surface-tension body force
+ * -gamma * kappa * grad H (any gamma; the Python surface routes gamma > 1e-12 here) */
+int rmt_momentum_step_rk4_st(rmt_ctx *ctx, const rmt_momentum_params *prm, double gamma,
+                             const double *u, const double *v, const double *p, const double *X1,
+                             const double *X2, const double *phi, double *u_new, double *v_new,
+                             double *sxx, double *sxy, double *syy, double *J);
+/* functions.py:765-834 momentum_step_rk4_2solids: two reference maps, the n = 2 mixture of
+ * the stresses and densities, the contact force as a body force (k_rep <= 0: none).  Of prm,
+ * eta_s and stress_band are unused (as in the reference) and detg_clamp bounds both solids'
+ * J.  Jmin = min(Ja, Jb). */
+int rmt_momentum_step_rk4_2solids(rmt_ctx *ctx, const rmt_momentum_params *prm, double k_rep,
+                                  double w_c, const double *u, const double *v, const double *p,
+                                  const double *X1a, const double *X2a, const double *X1b,
+                                  const double *X2b, const double *phi_a, const double *phi_b,
+                                  double *u_new, double *v_new, double *Jmin);
+
+/* The two pieces of the two-disc driver loop (benchmarks/two_disc_contact.py:80-84, :100-104)
+ * that are plain array expressions there: out = q * (phi <= 0), and the per-step record
+ * out5 = {cxa, cya, cxb, cyb, min Jmin} with disc_centroid of each level set over the node
+ * planes X, Y (host result, blocks; NaN centroid when a level set has no cell <= 0). */
+int rmt_mask_solid(rmt_ctx *ctx, const double *q, const double *phi, double *out);
+/* (Ha + Hb - 1) rho_f + (1 - Ha) rho_s + (1 - Hb) rho_s with H = smoothed_heaviside(phi, w_t)
+ * (functions.py:792-795, two_disc_contact.py:94-95) */
+int rmt_mixture_density(rmt_ctx *ctx, const double *phi_a, const double *phi_b, double w_t,
+                        double rho_s, double rho_f, double *rho);
+int rmt_two_solid_diag(rmt_ctx *ctx, const double *phi_a, const double *phi_b, const double *X,
+                       const double *Y, const double *Jmin, double *out5);
 
 /* librmt diagnostic (no reference counterpart): 0 (default) one LDS-tiled kernel per RK4
  * stage, 2 unfused per-cell passes.  Bit-identical results in both; other modes: RMT_EINVAL. */
@@ -206,6 +239,14 @@ int rmt_solve_poisson_dct(rmt_ctx *ctx, const double *rhs, double dx, double dy,
 int rmt_pressure_projection(rmt_ctx *ctx, const double *a_star, const double *b_star,
                             double dx, double dy, double dt, double rho, int bc_kind,
                             double lid, const double *p_prev, double *a, double *b, double *p);
+/* The same branch with rho a device (ny, nx) array that is constant only to rounding
+ * (0 < ptp <= 1e-10, e.g. the two-solid mixture density at rho_s == rho_f), taken pointwise
+ * as the reference does: d_f = dt / mean(rho), rhs = rho * divU / dt, a = a* - (dt / rho)
+ * grad p_c.  p_prev may be NULL. */
+int rmt_pressure_projection_rho_field(rmt_ctx *ctx, const double *a_star, const double *b_star,
+                                      double dx, double dy, double dt, const double *rho,
+                                      int bc_kind, double lid, const double *p_prev, double *a,
+                                      double *b, double *p);
 /* The variable-density branch (rho a device (ny, nx) array with ptp > 1e-10),
  * functions.py:1296-1328 + :1350-1364: Rhie-Chow divergence with per-face dt/rho, rhs =
  * divU/dt - mean, preconditioned CG (scipy.sparse.linalg.cg semantics: x0 = 0, stop when

@@ -95,6 +95,17 @@ SIGNATURES = {
     "rmt_apply_velocity_bc": (_I, [_P, _I, _D, _P, _P]),
     "rmt_momentum_step_rk4": (_I, [_P, ctypes.POINTER(rmt_momentum_params), _P, _P, _P, _P, _P,
                                    _P, _P, _P, _P, _P, _P, _P]),
+    "rmt_compute_curvature": (_I, [_P, _P, _D, _D, _P]),
+    "rmt_compute_contact_force": (_I, [_P, _P, _P, _D, _D, _D, _D, _P, _P]),
+    "rmt_momentum_step_rk4_st": (_I, [_P, ctypes.POINTER(rmt_momentum_params), _D, _P, _P, _P,
+                                      _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rmt_momentum_step_rk4_2solids": (_I, [_P, ctypes.POINTER(rmt_momentum_params), _D, _D, _P,
+                                           _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rmt_mask_solid": (_I, [_P, _P, _P, _P]),
+    "rmt_mixture_density": (_I, [_P, _P, _P, _D, _D, _D, _P]),
+    "rmt_two_solid_diag": (_I, [_P, _P, _P, _P, _P, _P, ctypes.POINTER(_D)]),
+    "rmt_pressure_projection_rho_field": (_I, [_P, _P, _P, _D, _D, _D, _P, _I, _D, _P, _P, _P,
+                                               _P]),
     "rmt_divergence_rc": (_I, [_P, _P, _P, _P, _D, _D, _D, _P]),
     "rmt_divergence_central": (_I, [_P, _P, _P, _D, _D, _P]),
     "rmt_pressure_gradient": (_I, [_P, _P, _D, _D, _P, _P]),

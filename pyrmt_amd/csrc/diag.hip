@@ -97,11 +97,11 @@ __global__ void __launch_bounds__(64) k_np_pairwise(const double *__restrict__ x
     if (lane == 0) part[blockIdx.x] = v;
 }
 
-// np.sum(x) for n cells: chunk partials on the device, then `s += chunk` on the host
-static int np_sum_host(rmt_ctx *ctx, const double *x, long n, double *out) {
+// np.sum(x) for n cells: chunk partials on the device (part: ceil(n / 8192) doubles), then
+// `s += chunk` on the host
+int np_sum(rmt_ctx *ctx, const double *x, long n, double *part, double *out) {
     const long nch = (n + NP_CHUNK - 1) / NP_CHUNK;
     RMT_CHECK(n > 0, RMT_EINVAL, "np_sum: empty array");
-    double *part = ctx->scratch + n;   // the density plane sits at ctx->scratch[0, n)
     k_np_pairwise<<<nch, 64, 0, ctx->stream>>>(x, n, part);
     RMT_LAUNCHED();
     std::vector<double> h(nch);
@@ -112,6 +112,10 @@ static int np_sum_host(rmt_ctx *ctx, const double *x, long n, double *out) {
     for (long k = 0; k < nch; ++k) s += h[k];
     *out = s;
     return RMT_OK;
+}
+// the density plane sits at ctx->scratch[0, n), the partials behind it
+static int np_sum_host(rmt_ctx *ctx, const double *x, long n, double *out) {
+    return np_sum(ctx, x, n, ctx->scratch + n, out);
 }
 
 // output.py:30-34: 0.5 * rho_local * (a**2 + b**2)

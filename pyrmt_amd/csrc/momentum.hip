@@ -1,4 +1,5 @@
 // momentum.hip -- functions.py:673-762 momentum_step_rk4 (gamma = 0) on MI355X.
+// (gamma > 0 and the two-solid step are momentum2.hip's general stage kernel.)
 //
 // Structure: one prep pass (elastic stress, smoothed Heaviside H, rho, solid mask), then
 // per RK4 stage three per-cell passes (stage velocity, blended stress, RHS), then the

@@ -599,6 +599,9 @@ int reduce_maxsq2_nan(rmt_ctx *ctx, const double *a, const double *b, long n, do
 int reduce_max_partials_nan(rmt_ctx *ctx, double *o);   // (RED_BLOCKS partials in ctx->red)
 int reduce_mean(rmt_ctx *ctx, const double *x, long n, double *dev_out);
 int read_scalar(rmt_ctx *ctx, const double *dev, double *host);
+// diag.hip: np.sum(x[0, n)) in numpy's own order (pairwise over 8192-element chunks, the chunk
+// sums added left to right); part: ceil(n / 8192) device doubles; host result, blocks
+int np_sum(rmt_ctx *ctx, const double *x, long n, double *part, double *out);
 // row-tree sums (ops.hip): root of rows [0, nrows) of x (row length nx) into *dev_root;
 // x -= tree(G roots) / count; and both for a whole (ny, nx) plane
 int rowtree_root(rmt_ctx *ctx, const double *x, int nrows, int nx, double *dev_root);

@@ -365,9 +365,9 @@ def apply_velocity_BCs(bc, u, v):
 
 def momentum_step_rk4(u, v, p, X1, X2, velocity_bc, mu_s, kappa, eta_s, dx, dy, dt, rho_s, rho_f,
                       phi, mu_f, w_t, gamma=0.0, stress_band=False, detg_clamp=3.0):
-    """functions.py:673-762.  Returns (u_new, v_new, sxx, sxy, syy, J)."""
-    if gamma > 1e-12:
-        raise NotImplementedError("surface tension (gamma > 0) is outside this build's path")
+    """functions.py:673-762.  Returns (u_new, v_new, sxx, sxy, syy, J).  gamma > 1e-12 adds
+    the surface-tension force -gamma * kappa * grad H (rmt_momentum_step_rk4_st); otherwise
+    the gamma = 0 path runs as before."""
     kind, lid = resolve_bc(velocity_bc)
     io = _IO(u, v, p, X1, X2, phi)
     u, v, p, X1, X2, phi = map(io.dev, (u, v, p, X1, X2, phi))
@@ -375,9 +375,55 @@ def momentum_step_rk4(u, v, p, X1, X2, velocity_bc, mu_s, kappa, eta_s, dx, dy, 
     prm = L.rmt_momentum_params(kind, lid, mu_s, kappa, eta_s, rho_s, rho_f, mu_f, w_t, dx, dy, dt,
                                 int(bool(stress_band)), detg_clamp)
     c = ctx_for(*u.shape)
+    if gamma > 1e-12:
+        L.check(L.lib().rmt_momentum_step_rk4_st(c.bind(), ctypes.byref(prm), float(gamma), _p(u),
+                                                 _p(v), _p(p), _p(X1), _p(X2), _p(phi),
+                                                 *map(_p, outs)), "momentum_step_rk4")
+        return tuple(io.out(o) for o in outs)
     L.check(L.lib().rmt_momentum_step_rk4(c.bind(), ctypes.byref(prm), _p(u), _p(v), _p(p), _p(X1),
                                           _p(X2), _p(phi), *map(_p, outs)), "momentum_step_rk4")
     return tuple(io.out(o) for o in outs)
+
+
+def momentum_step_rk4_2solids(u, v, p, X1a, X2a, X1b, X2b, velocity_bc, mu_s, kappa, eta_s, dx, dy,
+                              dt, rho_s, rho_f, phi_a, phi_b, mu_f, w_t, k_rep=0.0, w_c=None,
+                              detg_clamp=4.0):
+    """functions.py:765-834: RK4 momentum step for two neo-Hookean solids sharing one velocity
+    and pressure field, with the repulsive contact force (k_rep <= 0 disables it).  eta_s is
+    accepted and unused, as in the reference.  Returns (u_new, v_new, min(Ja, Jb))."""
+    if w_c is None:
+        w_c = 2.0 * w_t
+    kind, lid = resolve_bc(velocity_bc)
+    arrays = (u, v, p, X1a, X2a, X1b, X2b, phi_a, phi_b)
+    io = _IO(*arrays)
+    d = [io.dev(a) for a in arrays]
+    outs = [io.empty(d[0].shape) for _ in range(3)]
+    prm = L.rmt_momentum_params(kind, lid, mu_s, kappa, eta_s, rho_s, rho_f, mu_f, w_t, dx, dy, dt,
+                                0, detg_clamp)
+    c = ctx_for(*d[0].shape)
+    L.check(L.lib().rmt_momentum_step_rk4_2solids(c.bind(), ctypes.byref(prm), float(k_rep),
+                                                  float(w_c), *map(_p, d), *map(_p, outs)),
+            "momentum_step_rk4_2solids")
+    return tuple(io.out(o) for o in outs)
+
+
+def compute_curvature(phi, dx, dy):
+    """functions.py:837-861: kappa = div(grad(phi) / (|grad(phi)| + 1e-12))."""
+    io = _IO(phi); phi = io.dev(phi); out = io.empty(phi.shape)
+    c = ctx_for(*phi.shape)
+    L.check(L.lib().rmt_compute_curvature(c.bind(), _p(phi), dx, dy, _p(out)), "compute_curvature")
+    return io.out(out)
+
+
+def compute_contact_force(phi1, phi2, k_rep, w_c, dx, dy):
+    """functions.py:864-895: repulsive solid-solid contact body force (fx, fy)."""
+    io = _IO(phi1, phi2); phi1 = io.dev(phi1); phi2 = io.dev(phi2)
+    fx = io.empty(phi1.shape); fy = io.empty(phi1.shape)
+    c = ctx_for(*phi1.shape)
+    L.check(L.lib().rmt_compute_contact_force(c.bind(), _p(phi1), _p(phi2), float(k_rep),
+                                              float(w_c), dx, dy, _p(fx), _p(fy)),
+            "compute_contact_force")
+    return io.out(fx), io.out(fy)
 
 
 def momentum_mode(mode):
@@ -477,6 +523,19 @@ def _rho_scalar(rho):
     return r0
 
 
+def _near_constant_rho(rho):
+    """A 2D density array with 0 < ptp <= 1e-10 that is not exactly constant (the two-solid
+    mixture (Ha+Hb-1) rho_f + (1-Ha) rho_s + (1-Hb) rho_s at rho_s == rho_f is constant to one
+    ulp only): the reference takes its constant-density branch with the array pointwise
+    (functions.py:1049, :1331, :1352).  Returns the host copy, or None."""
+    if np.isscalar(rho) or not hasattr(rho, "ndim") or rho.ndim != 2:
+        return None
+    r = rho.detach().cpu().numpy() if hasattr(rho, "detach") else np.asarray(rho)
+    if np.ptp(r) > 1e-10 or np.all(r == r.flat[0]):
+        return None
+    return r
+
+
 def _is_variable_rho(rho):
     """functions.py:1026 / :1297: a 2D array whose ptp exceeds 1e-10."""
     if np.isscalar(rho) or not hasattr(rho, "ndim") or rho.ndim != 2:
@@ -494,7 +553,8 @@ def _compute_divergence_rc(a_star, b_star, p_prev, dt, rho, dx, dy):
         L.check(L.lib().rmt_divergence_rc_variable(c.bind(), _p(a), _p(b), _p(p), dt, _p(r), dx,
                                                    dy, _p(out)), "_compute_divergence_rc")
         return io.out(out)
-    r = _rho_scalar(rho)
+    near = _near_constant_rho(rho)
+    r = float(np.mean(near)) if near is not None else _rho_scalar(rho)   # d_f = dt / mean(rho)
     io = _IO(a_star, b_star, p_prev); a, b, p = map(io.dev, (a_star, b_star, p_prev))
     out = io.empty(a.shape)
     c = ctx_for(*a.shape)
@@ -657,6 +717,15 @@ def pressure_projection_amg(a_star, b_star, dx, dy, dt, rho, velocity_bc, A=None
     kind, lid = resolve_bc(velocity_bc)
     if _is_variable_rho(rho):
         return _projection_variable(a_star, b_star, dx, dy, dt, rho, kind, lid, A, ml, p_prev)
+    if _near_constant_rho(rho) is not None:
+        io = _IO(a_star, b_star, p_prev, rho)
+        a_s, b_s, pp, rd = map(io.dev, (a_star, b_star, p_prev, rho))
+        a = io.empty(a_s.shape); b = io.empty(a_s.shape); p = io.empty(a_s.shape)
+        c = ctx_for(*a_s.shape)
+        L.check(L.lib().rmt_pressure_projection_rho_field(
+            c.bind(), _p(a_s), _p(b_s), dx, dy, dt, _p(rd), kind, lid, _p(pp), _p(a), _p(b),
+            _p(p)), "pressure_projection_amg")
+        return io.out(a), io.out(b), io.out(p), A, ml
     r = _rho_scalar(rho)
     io = _IO(a_star, b_star, p_prev)
     a_s, b_s, pp = map(io.dev, (a_star, b_star, p_prev))

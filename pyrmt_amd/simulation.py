@@ -141,6 +141,105 @@ class Simulation:
         return {k: np.array([getattr(buf[i], k) for i in range(n.value)]) for k in keys}
 
 
+class TwoDiscContact:
+    """benchmarks/two_disc_contact.py: two neo-Hookean discs, each with its own reference map,
+    driven towards each other in a free-slip box; the repulsive contact force keeps them apart.
+    The loop body (two_disc_contact.py:70-104) runs on device tensors through the operators of
+    `functions` (composed in Python: one kernel sequence per operator, no fused step).
+
+    centres: the two discs' centres, as x coordinates (y = 0.5) or (x, y) pairs.
+    `record` holds one (t, dt, cxa, cxb, gap, min J) tuple per completed step."""
+
+    def __init__(self, N=128, centres=(0.30, 0.70), R=0.15, V0=0.15, k_rep=2.0, *, mu_s=1.0,
+                 kappa=0.0, rho_s=1.0, eta_s=0.0, mu_f=0.01, rho_f=1.0, w_t=None, w_c=None,
+                 cfl=0.2, dt_cap=1e-3, detg_clamp=4.0):
+        from .bc import Disc, FreeSlipBox
+        torch = F._torch()
+        self.torch = torch
+        self.N = N
+        X, Y, self.dx, self.dy = F.create_grid(N, N, 1.0, 1.0)
+        dx, dy = self.dx, self.dy
+        cs = [(float(c), 0.5) if np.ndim(c) == 0 else (float(c[0]), float(c[1])) for c in centres]
+        if len(cs) != 2:
+            raise ValueError("TwoDiscContact: two centres expected")
+        self.discs = [Disc(x0, y0, R) for x0, y0 in cs]
+        self.bc = FreeSlipBox()
+        self.k_rep = k_rep
+        self.mu_s, self.kappa, self.rho_s, self.eta_s = mu_s, kappa, rho_s, eta_s
+        self.mu_f, self.rho_f = mu_f, rho_f
+        self.w_t = 2.0 * dx if w_t is None else w_t
+        self.w_c = 3.0 * dx if w_c is None else w_c
+        self.cfl, self.dt_cap, self.detg_clamp = cfl, dt_cap, detg_clamp
+        self.layers = max(3, int(np.ceil(self.w_t / dx)) + 1)
+        # set-up on the host arrays, as the driver (two_disc_contact.py:37-59)
+        maps, Hs = [], []
+        for x0, y0 in cs:
+            phi = F.apply_phi_BCs(np.sqrt((X - x0) ** 2 + (Y - y0) ** 2) - R)
+            m = (phi <= 0).astype(float)
+            maps += list(F.extrapolate_reference_map(X * m, Y * m, phi, dx, dy, self.layers))
+            Hs.append(F.smoothed_heaviside(phi, self.w_t))
+        a, b = self.bc(V0 * (1 - Hs[0]) - V0 * (1 - Hs[1]), np.zeros((N, N)))
+        dev = lambda h: torch.from_numpy(np.ascontiguousarray(h)).cuda()
+        self.X, self.Y = dev(X), dev(Y)
+        self.X1a, self.X2a, self.X1b, self.X2b = map(dev, maps)
+        self.a, self.b, self.p = dev(a), dev(b), dev(np.zeros((N, N)))
+        self.phi_a = self.phi_b = self.Jmin = None
+        self.eig = F._precompute_poisson_eigenvalues(N, N, dx, dy)
+        self.ctx = F.ctx_for(N, N)
+        self.t = 0.0
+        self.record = []
+
+    def _advect(self, q, phi, dt):
+        """two_disc_contact.py:81-84: advect_reference_map(...) * (phi <= 0)"""
+        q = F.advect_reference_map(q, self.a, self.b, self.X, self.Y, dt, self.dx, self.dy, phi,
+                                   'semilagrangian', 0.0)
+        L.check(L.lib().rmt_mask_solid(self.ctx.bind(), F._p(q), F._p(phi), F._p(q)),
+                "rmt_mask_solid")
+        return q
+
+    def step(self, nsteps=1, t_end=math.inf):
+        dx, dy = self.dx, self.dy
+        for _ in range(int(nsteps)):
+            if not self.t < t_end:
+                break
+            dt = F.compute_timestep(self.a, self.b, dx, dy, self.cfl, self.dt_cap, self.mu_s,
+                                    self.rho_s, 0.0, self.rho_f, mu_f=self.mu_f, kappa=self.kappa)
+            if self.t + dt > t_end:
+                dt = t_end - self.t
+            da, db = self.discs
+            phi_a = F.rebuild_phi_from_reference_map(self.X1a, self.X2a, da)
+            phi_b = F.rebuild_phi_from_reference_map(self.X1b, self.X2b, db)
+            X1a = self._advect(self.X1a, phi_a, dt); X2a = self._advect(self.X2a, phi_a, dt)
+            X1b = self._advect(self.X1b, phi_b, dt); X2b = self._advect(self.X2b, phi_b, dt)
+            self.X1a, self.X2a = F.extrapolate_reference_map(X1a, X2a, phi_a, dx, dy, self.layers)
+            self.X1b, self.X2b = F.extrapolate_reference_map(X1b, X2b, phi_b, dx, dy, self.layers)
+            phi_a = F.rebuild_phi_from_reference_map(self.X1a, self.X2a, da)
+            phi_b = F.rebuild_phi_from_reference_map(self.X1b, self.X2b, db)
+            a_star, b_star, Jmin = F.momentum_step_rk4_2solids(
+                self.a, self.b, self.p, self.X1a, self.X2a, self.X1b, self.X2b, self.bc, self.mu_s,
+                self.kappa, self.eta_s, dx, dy, dt, self.rho_s, self.rho_f, phi_a, phi_b,
+                self.mu_f, self.w_t, k_rep=self.k_rep, w_c=self.w_c, detg_clamp=self.detg_clamp)
+            rho = self.torch.empty_like(phi_a)
+            h = self.ctx.bind()
+            L.check(L.lib().rmt_mixture_density(h, F._p(phi_a), F._p(phi_b), self.w_t, self.rho_s,
+                                                self.rho_f, F._p(rho)), "rmt_mixture_density")
+            self.a, self.b, self.p, _, _ = F.pressure_projection_amg(
+                a_star, b_star, dx, dy, dt, rho, velocity_bc=self.bc, p_prev=self.p,
+                eigenvalues=self.eig, bc_type='neumann')
+            out = (ctypes.c_double * 5)()
+            L.check(L.lib().rmt_two_solid_diag(self.ctx.bind(), F._p(phi_a), F._p(phi_b),
+                                               F._p(self.X), F._p(self.Y), F._p(Jmin), out),
+                    "rmt_two_solid_diag")
+            self.phi_a, self.phi_b, self.Jmin = phi_a, phi_b, Jmin
+            self.t += dt
+            self.record.append((self.t, dt, out[0], out[2], out[2] - out[0], out[4]))
+        return self
+
+    def get(self, name):
+        """A host copy of a, b, p, X1a, X2a, X1b, X2b, phi_a, phi_b or Jmin."""
+        return getattr(self, name).cpu().numpy()
+
+
 class _CAI:
     """__cuda_array_interface__ exporter of a librmt buffer.  torch.as_tensor keeps a strong
     reference to it in the tensor's storage (released when the storage is freed), so a weak
