@@ -79,7 +79,9 @@ int rmt_ctx_kernel_ms(rmt_ctx *ctx, double *ms2);
  * no_overlap, side_tail, par_overlap, fused_fixprep, merged_join, test_delay_side,
  * test_delay_main, chain_cols, chain_layer_groups, edge_slots, edge_stream, sl_phi,
  * mac_boxes, skip_marked_rows, tail_stream, diag_first, mac_noop_host, mac_face_sl,
- * mac_m2_bound, diag_seg, sl_zero_flags, dct_desc, and the test-only test_delay_geo / test_nowait_drop (a slab's
+ * mac_m2_bound, diag_seg, sl_zero_flags, dct_desc, dct_sym (both read when the context's DCT
+ * plan is made, at its first solve; they choose another FFT of the same DCT-I, equal to
+ * rounding, not bit for bit), and the test-only test_delay_geo / test_nowait_drop (a slab's
  * early geometry delayed; a dropped geometry not waited for).  Set them before creating a sim or slab on the context (sim_hiprio is read
  * at rmt_sim_create); a change ends a carried step state.
  * Unknown name: RMT_EINVAL. */
@@ -234,6 +236,14 @@ int rmt_pressure_gradient(rmt_ctx *ctx, const double *p, double dx, double dy, d
 /* functions.py:1107-1119 _solve_poisson_dct: idctn(dctn(rhs,1)/eig,1) - mean, with eig
  * the DCT-I symbol of functions.py:1091-1104 for this grid (dx, dy). */
 int rmt_solve_poisson_dct(rmt_ctx *ctx, const double *rhs, double dx, double dy, double *p);
+/* Test hook (no reference counterpart): the solve's plain row pass alone, on the LDS path
+ * (RMT_ENOTSUP otherwise): dst = scale * DCT-I of every row of src (device pointers, (ny, nx)).
+ * rowmark (nullable, ny bytes): only the rows marked (unmarked != 0: only the others), the rest
+ * of dst is left as it is.  rs (nullable, ny doubles, not with rowmark): the row sums the pass
+ * takes itself; rs_ref (nullable): the row sums of dst in the order of the projection's mean. */
+int rmt_selftest_dct_rows(rmt_ctx *ctx, const double *src, double dx, double dy, double scale,
+                          double *dst, double *rs, double *rs_ref,
+                          const unsigned char *rowmark, int unmarked);
 /* functions.py:1255-1364 pressure_projection_amg, Neumann branch, constant density rho
  * (variable density: rmt_pressure_projection_variable).  p_prev may be NULL. */
 int rmt_pressure_projection(rmt_ctx *ctx, const double *a_star, const double *b_star,

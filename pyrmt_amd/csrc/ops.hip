@@ -49,6 +49,7 @@ static const struct { const char *name, *env; int rmt_opts::*f; } kOpts[] = {
     {"diag_seg", "RMT_DIAG_SEG", &rmt_opts::diag_seg},
     {"sl_zero_flags", "RMT_SL_ZERO_FLAGS", &rmt_opts::sl_zero_flags},
     {"dct_desc", "RMT_DCT_DESC", &rmt_opts::dct_desc},
+    {"dct_sym", "RMT_DCT_SYM", &rmt_opts::dct_sym},
 };
 int g_list_blocks = getenv("RMT_LIST_BLOCKS") ? std::max(1, atoi(getenv("RMT_LIST_BLOCKS")))
                                                 : LIST_BLOCKS;
@@ -1054,6 +1055,18 @@ int rmt_pressure_gradient(rmt_ctx *ctx, const double *p, double dx, double dy, d
 }
 int rmt_solve_poisson_dct(rmt_ctx *ctx, const double *rhs, double dx, double dy, double *p) {
     return dct_solve(ctx, rhs, dx, dy, p);
+}
+int rmt_selftest_dct_rows(rmt_ctx *ctx, const double *src, double dx, double dy, double scale,
+                          double *dst, double *rs, double *rs_ref,
+                          const unsigned char *rowmark, int unmarked) {
+    RMT_CHECK(ctx && src && dst, RMT_EINVAL, "null argument");
+    RMT_TRY(dct_plan(ctx, dx, dy));
+    RMT_TRY(dct_pass(ctx, false, 0, src, dst, ctx->ny, 0, scale, rs, rowmark, unmarked != 0));
+    if (rs_ref) {
+        k_rowsum<<<ctx->ny, 256, 0, ctx->stream>>>(dst, ctx->nx, rs_ref);
+        RMT_LAUNCHED();
+    }
+    return RMT_OK;
 }
 int rmt_pressure_projection(rmt_ctx *ctx, const double *a_star, const double *b_star,
                             double dx, double dy, double dt, double rho, int bc_kind,

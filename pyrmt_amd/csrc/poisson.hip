@@ -17,6 +17,9 @@
 // HBM traffic: 10 planes per solve.  Reading the columns in place instead of transposing
 // (strided, XCD-grouped workgroups) measured slower: 380 us for the fused column pass
 // against 63 + 234 + 43 us with the transposes.  Other sizes: rocFFT R2C rounds.
+// An axis with n - 1 odd and a product of pairwise coprime radices 3 .. 13 (n = 4096) runs
+// k_dct1s instead of k_dct1 in the same launches: the even-symmetric prime-factor FFT on half
+// the row (32 KB, four workgroups per CU), see there.
 #include "rmt_internal.hpp"
 #include "dft_consts.hpp"
 #include <algorithm>
@@ -41,6 +44,9 @@ struct DctPlan {
     int mat = 0;                            // a matrix-form radix (29, 31) present
     double2 *Wx = nullptr, *Wy = nullptr;   // per-pass twiddle tables (twiddles())
     int radx[16] = {0}, rady[16] = {0}, npx = 0, npy = 0;
+    // half-row path (k_dct1s) per axis: pairwise coprime radices of n - 1 and the read-out table
+    int symx[4] = {0}, symy[4] = {0}, nsx = 0, nsy = 0;
+    unsigned short *tabx = nullptr, *taby = nullptr;
 };
 
 static bool g_rocfft_ready = false;
@@ -76,6 +82,7 @@ void dct_destroy(DctPlan *P) {
     (void)hipFree(P->work); (void)hipFree(P->E); (void)hipFree(P->C); (void)hipFree(P->T);
     (void)hipFree(P->lamx); (void)hipFree(P->lamy);
     (void)hipFree(P->Wx); (void)hipFree(P->Wy);
+    (void)hipFree(P->tabx); (void)hipFree(P->taby);
     delete P;
 }
 
@@ -162,6 +169,32 @@ static int twiddles(int M, const int *rad, int np, double2 **W, bool post = fals
     return RMT_OK;
 }
 
+// The half-row plan of an axis (k_dct1s; tools/dct_sym_model.py): N = n - 1 odd and a product
+// of pairwise coprime radices from {13, 11, 9, 7, 5, 3}, in that (pass) order.  4095 gives
+// 13, 9, 7, 5; four radices at the most below K1_MAXN.
+static bool sym_factor(int N, int *rad, int *np) {
+    int n = 0, m = N;
+    for (int R : {13, 11, 9, 7, 5, 3})
+        if (m % R == 0 && n < 4 && !(R == 3 && N % 9 == 0)) { rad[n++] = R; m /= R; }
+    *np = n;
+    return N >= 3 && N < K1_MAXN && m == 1;
+}
+// Its read-out table: the slot that holds C at frequency k (N + 1) / 2 after the in-place
+// prime-factor passes, k = 0 .. (N - 1) / 2 (slot(i) = min(i, N - i))
+static int sym_table(int N, const int *rad, int np, unsigned short **tab) {
+    std::vector<unsigned short> h((N + 1) / 2);
+    for (int k = 0; k <= (N - 1) / 2; ++k) {
+        const long k2 = (long)k * ((N + 1) / 2) % N;
+        long sig = 0;
+        for (int q = 0; q < np; ++q) sig += (k2 % rad[q]) * (N / rad[q]);
+        sig %= N;
+        h[k] = (unsigned short)std::min(sig, N - sig);
+    }
+    RMT_HIP(hipMalloc(tab, h.size() * sizeof(unsigned short)));
+    RMT_UPLOAD(*tab, h.data(), h.size() * sizeof(unsigned short));
+    return RMT_OK;
+}
+
 // LDS budget of one FFT workgroup: the length-M sequence + 4 KB static
 constexpr size_t FFT_LDS_MAX = 160 * 1024 - 4096;
 static bool lds_fits(int M) { return (size_t)M * sizeof(double2) <= FFT_LDS_MAX; }
@@ -182,12 +215,18 @@ int dct_plan(rmt_ctx *ctx, double dx, double dy) {
         P->mat = mat_radix(P->radx, P->npx) || mat_radix(P->rady, P->npy);
         // (a matrix pass needs a second length-M buffer: both planes within the LDS budget)
         if (P->mat) P->lds = P->lds && lds_fits(2 * Nx + 64) && lds_fits(2 * Ny + 64);
+        // dct_sym: an eligible axis of the LDS path runs on half the row (every eligible
+        // length also has a k_dct1 plan, so P->lds is decided as before)
+        if (!(P->lds && ctx->opt.dct_sym && sym_factor(Nx, P->symx, &P->nsx))) P->nsx = 0;
+        if (!(P->lds && ctx->opt.dct_sym && sym_factor(Ny, P->symy, &P->nsy))) P->nsy = 0;
     }
     if (!P->lds && !g_rocfft_ready) { RMT_TRY(rf(rocfft_setup(), "setup")); g_rocfft_ready = true; }
     if (P->lds && !P->Wx) {
         const size_t n = (size_t)P->ny * P->nx;
         RMT_TRY(twiddles(P->nx - 1, P->radx, P->npx, &P->Wx, true));
         RMT_TRY(twiddles(P->ny - 1, P->rady, P->npy, &P->Wy, true));
+        if (P->nsx) RMT_TRY(sym_table(P->nx - 1, P->symx, P->nsx, &P->tabx));
+        if (P->nsy) RMT_TRY(sym_table(P->ny - 1, P->symy, P->nsy, &P->taby));
         RMT_HIP(hipMalloc(&P->T, n * sizeof(double)));
         RMT_HIP(hipMalloc(&P->lamx, P->nx * sizeof(double)));
         RMT_HIP(hipMalloc(&P->lamy, P->ny * sizeof(double)));
@@ -701,6 +740,196 @@ __global__ void __launch_bounds__(K1T<BIG>::T, BIG ? 2 : 4) k_dct1(const double 
     }
 }
 
+// ------------------------------------------------ DCT-I on half the row (k_dct1s) --
+// k_dct1 uses that the even extension e is real; this kernel also uses that it is even
+// (tools/dct_sym_model.py states the index maps in numpy).  For N = n - 1
+// odd, 2N = 2 N is a coprime split (Good-Thomas): the even- and odd-index halves a, b of e,
+// indexed by m = j mod N, are real and even, so their length-N DFTs A, B are real and ONE
+// complex DFT of c = a + i b gives both:  c_m = (x_m, x_{N-m}) for even m, (x_{N-m}, x_m) for
+// odd m, and  X_k = Re C + (-1)^k Im C,  X_{N-k} = Re C - (-1)^k Im C  at  C = C_{k (N+1)/2}.
+// c_{N-m} = c_m, and every stage of the transform keeps that symmetry, so LDS holds only
+// slot(i) = min(i, N - i), i.e. (N + 1) / 2 complex values: 32 KB for n = 4096.  With N a
+// product of pairwise coprime radices the DFT is the prime-factor algorithm in place: radix R
+// (s = N / R) transforms the lines (R q + j s) mod N, j < R, with dft<R> and no twiddles; line
+// s - q mirrors line q, so q = 0 .. (s - 1) / 2 are computed, and line 0, its own mirror,
+// writes k <= (R - 1) / 2.  No twiddle table, no packed-real split; the read-out order is a
+// table of 16-bit slots (sym_table).  256 threads per row, four workgroups per CU.
+constexpr int K1S_T = 256;
+struct SymRad { int R[4]; int n; };
+
+template <int R, int NT, int NMAX>
+__device__ __forceinline__ void sym_pass(double2 *z, const int N, const int s) {
+    constexpr int LPT = ((NMAX / R + 1) / 2 + NT - 1) / NT;   // lines per thread (max)
+    const int nl = (s + 1) / 2;
+    // opaque per pass, as in fft_pass
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    double2 v[LPT][R];
+#pragma unroll
+    for (int b = 0; b < LPT; ++b) {
+        const int q = tid + b * NT;
+        if (q < nl) {
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                int i = R * q + j * s;   // < 3 N / 2
+                if (i >= N) i -= N;
+                v[b][j] = z[min(i, N - i)];
+            }
+        }
+    }
+    __syncthreads();
+    // (opaque again: the R slot addresses are formed anew, not held across the butterfly)
+    asm volatile("" : "+v"(tid));
+#pragma unroll
+    for (int b = 0; b < LPT; ++b) {
+        const int q = tid + b * NT;
+        if (q < nl) {
+            dft<R>(v[b]);
+#pragma unroll
+            for (int k = 0; k < R; ++k) {
+                int i = R * q + k * s;
+                if (i >= N) i -= N;
+                if (k <= R / 2 || q != 0) z[min(i, N - i)] = v[b][k];
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// same interface as k_dct1 (rows, SOLVE, row0, scale, rs, rowmark / rm_inv); K4095: the
+// n = 4096 plan 13, 9, 7, 5 with constant index math
+template <bool SOLVE, bool K4095>
+__global__ void __launch_bounds__(K1S_T, 4) k_dct1s(const double *__restrict__ src,
+                                                    double *__restrict__ dst, int rows, int n,
+                                                    const unsigned short *__restrict__ tab,
+                                                    SymRad sr, double scale,
+                                                    const double *__restrict__ lamr,
+                                                    const double *__restrict__ lamk, int row0,
+                                                    double *__restrict__ rs,
+                                                    const unsigned char *__restrict__ rowmark,
+                                                    int rm_inv = 0) {
+    if (rowmark && (rowmark[blockIdx.x] != 0) == (rm_inv != 0)) return;
+    constexpr int NT = K1S_T;
+    // slots per thread, (N + 1) / 2 <= K1_MAXN / 2 (K4095: exactly PP each, no guards)
+    constexpr int PP = (K1_MAXN / 2 + NT - 1) / NT;
+    extern __shared__ double2 z[];
+    __shared__ double red[256];
+    const int N = K4095 ? 4095 : n - 1, H = N / 2, r = blockIdx.x;
+    double *d = (double *)z;
+    {
+        // every load issued before the first LDS write (put_row_even)
+        const double *x = src + (long)r * n;
+        double va[PP], vb[PP];
+#pragma unroll
+        for (int t = 0; t < PP; ++t) {
+            const int m = threadIdx.x + t * NT;
+            if (K4095 || m <= H) { va[t] = x[m]; vb[t] = x[N - m]; }
+        }
+#pragma unroll
+        for (int t = 0; t < PP; ++t) {
+            const int m = threadIdx.x + t * NT;
+            if (K4095 || m <= H) z[m] = (m & 1) ? make_double2(vb[t], va[t]) : make_double2(va[t], vb[t]);
+        }
+    }
+#pragma unroll 1
+    for (int it = 0; it < (SOLVE ? 2 : 1); ++it) {
+        __syncthreads();
+        if constexpr (K4095) {
+            sym_pass<13, NT, 4095>(z, 4095, 315);
+            sym_pass<9, NT, 4095>(z, 4095, 455);
+            sym_pass<7, NT, 4095>(z, 4095, 585);
+            sym_pass<5, NT, 4095>(z, 4095, 819);
+        } else {
+            for (int q = 0; q < sr.n; ++q) {
+                const int s = N / sr.R[q];
+                switch (sr.R[q]) {
+                    case 3: sym_pass<3, NT, K1_MAXN>(z, N, s); break;
+                    case 5: sym_pass<5, NT, K1_MAXN>(z, N, s); break;
+                    case 7: sym_pass<7, NT, K1_MAXN>(z, N, s); break;
+                    case 9: sym_pass<9, NT, K1_MAXN>(z, N, s); break;
+                    case 11: sym_pass<11, NT, K1_MAXN>(z, N, s); break;
+                    case 13: sym_pass<13, NT, K1_MAXN>(z, N, s); break;
+                }
+            }
+        }
+        // opaque per iteration: the table / eigenvalue loads below, indexed from it, are not
+        // hoisted above the passes
+        const unsigned short *tb = tab;
+        const double *lr = lamr, *lk = lamk;
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        int sl[PP];
+#pragma unroll
+        for (int t = 0; t < PP; ++t) {
+            const int k = tid + t * NT;
+            if (K4095 || k <= H) sl[t] = tb[k];
+        }
+        double xa[PP], xb[PP];   // X_k, X_{N-k} for k = tid + t NT <= H
+#pragma unroll
+        for (int t = 0; t < PP; ++t) {
+            const int k = tid + t * NT;
+            if (K4095 || k <= H) {
+                const double2 C = z[sl[t]];
+                const double im = (k & 1) ? -C.y : C.y;
+                xa[t] = C.x + im;
+                xb[t] = C.x - im;
+            } else {
+                xa[t] = xb[t] = 0.0;   // (defined on every path: not carried round the loop)
+            }
+        }
+        if (SOLVE && it == 0) {
+            const int kx = row0 + r;
+            const double lx = lr[kx];
+#pragma unroll
+            for (int t = 0; t < PP; ++t) {
+                const int k = tid + t * NT;
+                if (K4095 || k <= H) {
+                    const double ea = (kx == 0 && k == 0) ? 1.0 : lx + lk[k];
+                    xa[t] = xa[t] / ea;
+                    xb[t] = xb[t] / (lx + lk[N - k]);
+                }
+                // one pair's divisions at a time (k_dct1)
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            __syncthreads();   // every C read
+            // the thread holding X_k and X_{N-k} holds the pair c_k of the inverse transform
+#pragma unroll
+            for (int t = 0; t < PP; ++t) {
+                const int k = tid + t * NT;
+                if (K4095 || k <= H) z[k] = (k & 1) ? make_double2(xb[t], xa[t]) : make_double2(xa[t], xb[t]);
+            }
+            continue;
+        }
+        double *o = dst + (long)r * n;
+#pragma unroll
+        for (int t = 0; t < PP; ++t) {
+            const int k = tid + t * NT;
+            if (K4095 || k <= H) { o[k] = xa[t] * scale; o[N - k] = xb[t] * scale; }
+        }
+        if (rs) {
+            // the sum k_rowsum would take of the row written: 256 strided partials, then the
+            // halving tree (ops.hip); the row staged in the n doubles of z
+            __syncthreads();
+#pragma unroll
+            for (int t = 0; t < PP; ++t) {
+                const int k = tid + t * NT;
+                if (K4095 || k <= H) { d[k] = xa[t] * scale; d[N - k] = xb[t] * scale; }
+            }
+            __syncthreads();
+            double acc = 0.0;
+            for (int k = tid; k < n; k += 256) acc += d[k];
+            red[tid] = acc;
+            __syncthreads();
+            for (int w = 128; w > 0; w >>= 1) {
+                if (tid < w) red[tid] = red[tid] + red[tid + w];
+                __syncthreads();
+            }
+            if (tid == 0) rs[r] = red[0];
+        }
+    }
+}
+static_assert(K1S_T == 256, "k_dct1s: the row sum is k_rowsum's, 256 partials");
+
 // out (C x R) = in (R x C) transposed, 64 x 64 tiles through LDS.  rowmark (nullable) with
 // mode 1: only the 64-row blocks of in holding no marked row; mode 2: only those holding one
 __global__ void __launch_bounds__(256) k_transpose(const double *__restrict__ in, int R, int C,
@@ -765,6 +994,26 @@ int dct_pass(rmt_ctx *ctx, bool solve, int axis, const double *src, double *dst,
     const size_t lds = (size_t)(P->mat ? 2 * (n - 1) + 32 : n - 1) * sizeof(double2);
     const unsigned g = (unsigned)nrows;   // one row per workgroup
     hipStream_t st = ctx->stream;
+    if (const int ns = axis == 0 ? P->nsx : P->nsy) {
+        // this axis runs on half the row (dct_sym): n doubles of LDS
+        const int *sym = axis == 0 ? P->symx : P->symy;
+        const unsigned short *tab = axis == 0 ? P->tabx : P->taby;
+        SymRad sr{};
+        for (int k = 0; k < ns; ++k) sr.R[k] = sym[k];
+        sr.n = ns;
+        const size_t ldh = (size_t)n * sizeof(double);
+        const bool k4095 = n == 4096;   // sym_factor(4095): 13, 9, 7, 5
+        if (solve && k4095)
+            k_dct1s<true, true><<<g, K1S_T, ldh, st>>>(src, dst, nrows, n, tab, sr, scale, P->lamx, P->lamy, row0, nullptr, nullptr);
+        else if (solve)
+            k_dct1s<true, false><<<g, K1S_T, ldh, st>>>(src, dst, nrows, n, tab, sr, scale, P->lamx, P->lamy, row0, nullptr, nullptr);
+        else if (k4095)
+            k_dct1s<false, true><<<g, K1S_T, ldh, st>>>(src, dst, nrows, n, tab, sr, scale, nullptr, nullptr, 0, rs, rowmark, unmarked);
+        else
+            k_dct1s<false, false><<<g, K1S_T, ldh, st>>>(src, dst, nrows, n, tab, sr, scale, nullptr, nullptr, 0, rs, rowmark, unmarked);
+        RMT_LAUNCHED();
+        return RMT_OK;
+    }
     const bool k4095 = n == 4096 && !P->big && np == 4 && rad[0] == 5 &&
                        rad[1] == 7 && rad[2] == 9 && rad[3] == 13;   // fft_4095's plan
     const bool k4095d = n == 4096 && !P->big && np == 4 && rad[0] == 13 &&

@@ -116,6 +116,8 @@ struct rmt_opts {
                               // can hold a solid cell or J != 1 (k_diag_seg)
     int dct_desc = 1;         // RMT_DCT_DESC: n = 4096 DCT-I plan 13, 9, 7, 5 (fft_4095d;
                               // 0: 5, 7, 9, 13, fft_4095)
+    int dct_sym = 1;          // RMT_DCT_SYM: a DCT-I axis with n - 1 odd and a product of pairwise
+                              // coprime radices 3 .. 13 runs on half the row (k_dct1s; 0: k_dct1)
     int sl_zero_flags = 1;    // RMT_SL_ZERO_FLAGS: the side SL pass skips the loads and stores of
                               // tiles whose map stays +0.0 (zero-tile flags, k_sim_sl_t)
 };
