@@ -14,8 +14,7 @@
 // reductions, so iterates agree with NumPy/BLAS to rounding.  The DST-II (ortho) of a row of
 // M values is the imaginary part of a rotated length-2M complex FFT of its odd extension
 // (rocFFT, batched over rows; the other axis through a transpose).
-#include "rmt_internal.hpp"
-#include <rocfft/rocfft.h>
+#include "rocfft_util.hpp"
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -234,10 +233,7 @@ __global__ void __launch_bounds__(256) k_im_transpose(const double *__restrict__
 struct DstAxis {
     int M = 0;
     long rows = 0;
-    rocfft_plan fwd = nullptr, inv = nullptr;
-    rocfft_execution_info info = nullptr;
-    void *work = nullptr;
-    size_t work_bytes = 0;
+    RocfftPlans fft;         // [0] forward, [1] backward
     double2 *tw = nullptr;   // (cos, -sin)(pi m / 2M), m = 0 .. M
 };
 struct ImexPlan {
@@ -250,39 +246,18 @@ struct ImexPlan {
     std::vector<double> denom_h;   // host copy of denom (source of its async upload)
 };
 
-static bool g_rocfft = false;
-static int rfok(rocfft_status s, const char *what) {
-    if (s != rocfft_status_success) {
-        set_error(std::string("rocFFT ") + what + " failed");
-        return RMT_EDEVICE;
-    }
-    return RMT_OK;
-}
-static void axis_destroy(DstAxis &a) {
-    if (a.fwd) rocfft_plan_destroy(a.fwd);
-    if (a.inv) rocfft_plan_destroy(a.inv);
-    if (a.info) rocfft_execution_info_destroy(a.info);
-    (void)hipFree(a.work); (void)hipFree(a.tw);
-    a = DstAxis{};
-}
 static int axis_make(DstAxis &a, int M, long rows) {
     a.M = M; a.rows = rows;
     const size_t len = 2 * (size_t)M;
-    RMT_TRY(rfok(rocfft_plan_create(&a.fwd, rocfft_placement_inplace,
-                                    rocfft_transform_type_complex_forward, rocfft_precision_double,
-                                    1, &len, (size_t)rows, nullptr), "plan"));
-    RMT_TRY(rfok(rocfft_plan_create(&a.inv, rocfft_placement_inplace,
-                                    rocfft_transform_type_complex_inverse, rocfft_precision_double,
-                                    1, &len, (size_t)rows, nullptr), "plan"));
-    size_t w1 = 0, w2 = 0;
-    rocfft_plan_get_work_buffer_size(a.fwd, &w1);
-    rocfft_plan_get_work_buffer_size(a.inv, &w2);
-    a.work_bytes = std::max(w1, w2);
-    RMT_TRY(rfok(rocfft_execution_info_create(&a.info), "execution_info"));
-    if (a.work_bytes) {
-        RMT_HIP(hipMalloc(&a.work, a.work_bytes));
-        RMT_TRY(rfok(rocfft_execution_info_set_work_buffer(a.info, a.work, a.work_bytes), "work"));
-    }
+    RMT_TRY(rocfft_ok(rocfft_plan_create(&a.fft.plan[0], rocfft_placement_inplace,
+                                         rocfft_transform_type_complex_forward,
+                                         rocfft_precision_double, 1, &len, (size_t)rows, nullptr),
+                      "DST plan"));
+    RMT_TRY(rocfft_ok(rocfft_plan_create(&a.fft.plan[1], rocfft_placement_inplace,
+                                         rocfft_transform_type_complex_inverse,
+                                         rocfft_precision_double, 1, &len, (size_t)rows, nullptr),
+                      "DST plan"));
+    RMT_TRY(a.fft.finish());
     const long double PI = 3.141592653589793238462643383279502884L;
     std::vector<double2> h(M + 1);
     for (int m = 0; m <= M; ++m) {
@@ -297,7 +272,7 @@ static int axis_make(DstAxis &a, int M, long rows) {
 // the plans live on the context (ctx->imex[kind], kind 0 u, 1 v), freed with it
 static void plan_destroy(ImexPlan *P) {
     if (!P) return;
-    axis_destroy(P->ax[0]); axis_destroy(P->ax[1]);
+    (void)hipFree(P->ax[0].tw); (void)hipFree(P->ax[1].tw);
     (void)hipFree(P->denom); (void)hipFree(P->buf); (void)hipFree(P->T);
     delete P;
 }
@@ -313,7 +288,7 @@ static int imex_plan(rmt_ctx *ctx, int kind, int ny, int nx, double dx, double d
         *out = P;
         return RMT_OK;
     }
-    if (!g_rocfft) { RMT_TRY(rfok(rocfft_setup(), "setup")); g_rocfft = true; }
+    RMT_TRY(rocfft_ready());
     const bool keep = P && P->ny == ny && P->nx == nx;
     if (!keep) { plan_destroy(P); P = new ImexPlan; ctx->imex[kind] = P; }
     P->ny = ny; P->nx = nx; P->kind = kind; P->dx = dx; P->dy = dy; P->coef = coef;
@@ -343,15 +318,15 @@ static int imex_plan(rmt_ctx *ctx, int kind, int ny, int nx, double dx, double d
 // in-place DST-II (inv = false) or its inverse along the rows of x (rows x M), ortho
 static int dst_rows(hipStream_t st, DstAxis &a, double2 *buf, double *x, bool inv) {
     const long n = a.rows * a.M;
-    RMT_TRY(rfok(rocfft_execution_info_set_stream(a.info, st), "stream"));
+    RMT_TRY(a.fft.on(st));
     void *bp[1] = {buf};
     if (!inv) {
         k_dst_pack_fwd<<<grid1d(n, 256), 256, 0, st>>>(x, a.M, a.rows, buf);
-        RMT_TRY(rfok(rocfft_execute(a.fwd, bp, nullptr, a.info), "execute"));
+        RMT_TRY(rocfft_ok(rocfft_execute(a.fft.plan[0], bp, nullptr, a.fft.info), "DST execute"));
         k_dst_unpack_fwd<<<grid1d(n, 256), 256, 0, st>>>(buf, a.M, a.rows, a.tw, x);
     } else {
         k_dst_pack_inv<<<grid1d(2 * n, 256), 256, 0, st>>>(x, a.M, a.rows, a.tw, buf);
-        RMT_TRY(rfok(rocfft_execute(a.inv, bp, nullptr, a.info), "execute"));
+        RMT_TRY(rocfft_ok(rocfft_execute(a.fft.plan[1], bp, nullptr, a.fft.info), "DST execute"));
         k_dst_unpack_inv<<<grid1d(n, 256), 256, 0, st>>>(buf, a.M, a.rows, x);
     }
     RMT_LAUNCHED();

@@ -10,7 +10,7 @@
 //   k_mac_stress    sum_k (1 - H_k) sigma_k + pair contact stresses, J range  :79-89
 //   k_mac_predict   explicit MAC predictor with the face force 1/2 (div S_l + div S_r)
 //                   computed in place from S (fu / fv never stored)        :91-94
-//   k_mac_rhs       rhs = (rho/dt) div u*; row-tree mean removed; DCT-II solve (poisson.hip)
+//   k_mac_rhs       rhs = (rho/dt) div u*; row-tree mean removed; DCT-II solve (dct2.hip)
 //   k_mac_correct   u = u* - (dt/rho) grad phi on the interior faces            mac.py:126-139
 //   k_mac_diag      per-disc centroids over phi <= 0, max|u|
 // Every formula keeps the reference's NumPy operation order; only sin (H), the DCT and the

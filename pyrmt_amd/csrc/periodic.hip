@@ -7,7 +7,7 @@
 // (rocFFT D2Z / Z2D, the reference uses numpy.fft), divided by the separable symbol
 // -sin^2(2 pi k / m) / h^2 per axis with the null modes (|eig| < 1e-12: constant and
 // Nyquist) zeroed; means by the row-tree reduction.
-#include "rmt_internal.hpp"
+#include "rocfft_util.hpp"
 #include <algorithm>
 #include <vector>
 
@@ -15,27 +15,13 @@ namespace rmt {
 
 struct PerPlan {
     int m = 0;
-    rocfft_plan fwd = nullptr, inv = nullptr;
-    rocfft_execution_info info = nullptr;
-    void *work = nullptr;
-    size_t work_bytes = 0;
+    RocfftPlans fft;   // [0] D2Z, [1] Z2D
     double *red = nullptr, *C = nullptr, *lamx = nullptr, *lamy = nullptr, *g = nullptr;
 };
 
-static int rfc(rocfft_status s, const char *what) {
-    if (s != rocfft_status_success) {
-        set_error(std::string("rocFFT (periodic): ") + what + " failed");
-        return RMT_EDEVICE;
-    }
-    return RMT_OK;
-}
-
 void per_destroy(PerPlan *P) {
     if (!P) return;
-    if (P->fwd) rocfft_plan_destroy(P->fwd);
-    if (P->inv) rocfft_plan_destroy(P->inv);
-    if (P->info) rocfft_execution_info_destroy(P->info);
-    (void)hipFree(P->work); (void)hipFree(P->red); (void)hipFree(P->C); (void)hipFree(P->lamx); (void)hipFree(P->lamy);
+    (void)hipFree(P->red); (void)hipFree(P->C); (void)hipFree(P->lamx); (void)hipFree(P->lamy);
     (void)hipFree(P->g);
     delete P;
 }
@@ -48,24 +34,17 @@ static int per_plan(rmt_ctx *ctx, const double *lamx, const double *lamy) {
         if (P) per_destroy(P);
         P = ctx->per = new PerPlan;
         P->m = m;
-        static bool setup = false;
-        if (!setup) { RMT_TRY(rfc(rocfft_setup(), "setup")); setup = true; }
+        RMT_TRY(rocfft_ready());
         const size_t len[2] = {(size_t)m, (size_t)m};
-        RMT_TRY(rfc(rocfft_plan_create(&P->fwd, rocfft_placement_notinplace,
-                                       rocfft_transform_type_real_forward,
-                                       rocfft_precision_double, 2, len, 1, nullptr), "plan fwd"));
-        RMT_TRY(rfc(rocfft_plan_create(&P->inv, rocfft_placement_notinplace,
-                                       rocfft_transform_type_real_inverse,
-                                       rocfft_precision_double, 2, len, 1, nullptr), "plan inv"));
-        size_t w1 = 0, w2 = 0;
-        rocfft_plan_get_work_buffer_size(P->fwd, &w1);
-        rocfft_plan_get_work_buffer_size(P->inv, &w2);
-        P->work_bytes = std::max(w1, w2);
-        if (P->work_bytes) RMT_HIP(hipMalloc(&P->work, P->work_bytes));
-        RMT_TRY(rfc(rocfft_execution_info_create(&P->info), "execution_info_create"));
-        if (P->work_bytes)
-            RMT_TRY(rfc(rocfft_execution_info_set_work_buffer(P->info, P->work, P->work_bytes),
-                        "set_work_buffer"));
+        RMT_TRY(rocfft_ok(rocfft_plan_create(&P->fft.plan[0], rocfft_placement_notinplace,
+                                             rocfft_transform_type_real_forward,
+                                             rocfft_precision_double, 2, len, 1, nullptr),
+                          "periodic plan fwd"));
+        RMT_TRY(rocfft_ok(rocfft_plan_create(&P->fft.plan[1], rocfft_placement_notinplace,
+                                             rocfft_transform_type_real_inverse,
+                                             rocfft_precision_double, 2, len, 1, nullptr),
+                          "periodic plan inv"));
+        RMT_TRY(P->fft.finish());
         RMT_HIP(hipMalloc(&P->red, (size_t)m * m * sizeof(double)));
         RMT_HIP(hipMalloc(&P->C, (size_t)m * (m / 2 + 1) * 2 * sizeof(double)));
         RMT_HIP(hipMalloc(&P->lamx, m * sizeof(double)));
@@ -151,14 +130,14 @@ static int per_solve(rmt_ctx *ctx, const double *rhs, double s, double dt, doubl
     k_per_extract<<<grid1d(nr, 256), 256, 0, st>>>(rhs, N, s, dt, P->red);
     RMT_LAUNCHED();
     RMT_TRY(sub_mean_rows(ctx, P->red, m, m));                       // r -= mean(r)
-    RMT_TRY(rfc(rocfft_execution_info_set_stream(P->info, st), "set_stream"));
+    RMT_TRY(P->fft.on(st));
     void *in[1] = {P->red}, *out[1] = {P->C};
-    RMT_TRY(rfc(rocfft_execute(P->fwd, in, out, P->info), "execute fwd"));
+    RMT_TRY(rocfft_ok(rocfft_execute(P->fft.plan[0], in, out, P->fft.info), "periodic execute fwd"));
     k_per_divide<<<grid1d((long)m * (m / 2 + 1), 256), 256, 0, st>>>((double2 *)P->C, m, P->lamx,
                                                                        P->lamy);
     RMT_LAUNCHED();
     void *in2[1] = {P->C}, *out2[1] = {P->red};
-    RMT_TRY(rfc(rocfft_execute(P->inv, in2, out2, P->info), "execute inv"));
+    RMT_TRY(rocfft_ok(rocfft_execute(P->fft.plan[1], in2, out2, P->fft.info), "periodic execute inv"));
     k_per_tile<<<grid1d(nn, 256), 256, 0, st>>>(P->red, N, 1.0 / ((double)m * m), p);
     RMT_LAUNCHED();
     return sub_mean_rows(ctx, p, N, N);                              // p -= mean(p)

@@ -67,8 +67,8 @@ void set_error(const std::string &msg);
 #define RMT_TRY(expr)                                                                   \
     do { int s_ = (expr); if (s_ != RMT_OK) return s_; } while (0)
 
-struct DctPlan;   // poisson.hip (DCT-I, collocated grid)
-struct Dct2Plan;  // poisson.hip (DCT-II, MAC grid)
+struct DctPlan;   // dct1.hip (DCT-I, collocated grid)
+struct Dct2Plan;  // dct2.hip (DCT-II, MAC grid)
 struct PerPlan;   // periodic.hip (reduced-grid 2D FFT)
 
 }  // namespace rmt
@@ -114,8 +114,6 @@ struct rmt_opts {
     int mac_m2_bound = 1;     // RMT_MAC_M2_BOUND: MAC SL bound from the last correction's face maxima
     int diag_seg = 1;         // RMT_DIAG_SEG: the step's diagnostics read only the segments that
                               // can hold a solid cell or J != 1 (k_diag_seg)
-    int dct_desc = 1;         // RMT_DCT_DESC: n = 4096 DCT-I plan 13, 9, 7, 5 (fft_4095d;
-                              // 0: 5, 7, 9, 13, fft_4095)
     int dct_sym = 1;          // RMT_DCT_SYM: a DCT-I axis with n - 1 odd and a product of pairwise
                               // coprime radices 3 .. 13 runs on half the row (k_dct1s; 0: k_dct1)
     int sl_zero_flags = 1;    // RMT_SL_ZERO_FLAGS: the side SL pass skips the loads and stores of
@@ -736,7 +734,7 @@ int fixup_phi_prep(rmt_ctx *ctx, const rmt_momentum_params *P, const MomWork &W,
                    int max_tiles, const int *st_src = nullptr, int *st_dst = nullptr,
                    hipEvent_t done = nullptr);
 
-// ---------------------------------------------------------------------- poisson --
+// ------------------------------------------------- poisson (dct1.hip, dct2.hip) --
 // dev_root: nullptr -> p = solve - mean (functions.py:1119); else p = the raw solve and
 // *dev_root = its row-tree sum (mean = *dev_root / (ny nx), the caller subtracts it as it
 // reads p), or 0 when the mean was subtracted already (rocFFT path)

@@ -1,6 +1,6 @@
 // varrho.hip -- the variable-density branch of pressure_projection_amg:
 // functions.py:1296-1328 with the matrix-free operator of :1122-1168, preconditioned
-// conjugate gradients with the DCT-I solve (poisson.hip) as the preconditioner.
+// conjugate gradients with the DCT-I solve (dct1.hip) as the preconditioner.
 //
 //   rhs = divU_rc(rho) / dt - mean          functions.py:1016-1070 (per-face d_f), :1302-1303
 //   CG (x0 = 0, ||r|| < rtol ||b||, maxiter) scipy.sparse.linalg.cg (scipy 1.15 algorithm)

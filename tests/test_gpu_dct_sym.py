@@ -1,4 +1,4 @@
-"""k_dct1s (pyrmt_amd/csrc/poisson.hip, switch dct_sym): the DCT-I of an axis whose n - 1 is
+"""k_dct1s (pyrmt_amd/csrc/dct1.hip, switch dct_sym): the DCT-I of an axis whose n - 1 is
 odd with pairwise coprime radices 3 .. 13, as one even complex prime-factor DFT on half the
 row.  The solve against the oracle's pocketfft solve with the switch on and off, and the
 row pass's own row sums and row marks (rmt_selftest_dct_rows)."""

@@ -143,6 +143,8 @@ def test_option_names_and_errors(gpu):
     assert c.get_option("chain_layer_groups") == 2
     with pytest.raises(Exception, match="unknown option"):
         c.set_option("no_such_switch", 1)
+    with pytest.raises(Exception, match="unknown option"):
+        c.set_option("dct_desc", 0)   # retired: the n = 4096 plan is always 13, 9, 7, 5
 
 
 CHILD = r"""

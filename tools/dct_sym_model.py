@@ -1,4 +1,4 @@
-"""CPU model of k_dct1s (pyrmt_amd/csrc/poisson.hip): the DCT-I of a real row of length n,
+"""CPU model of k_dct1s (pyrmt_amd/csrc/dct1.hip): the DCT-I of a real row of length n,
 N = n - 1 odd with pairwise coprime radices, as ONE even complex length-N DFT held on half
 its indices.  The index maps here are the kernel's.
 
