@@ -79,7 +79,8 @@ int rmt_ctx_kernel_ms(rmt_ctx *ctx, double *ms2);
  * no_overlap, side_tail, par_overlap, fused_fixprep, merged_join, test_delay_side,
  * test_delay_main, chain_cols, chain_layer_groups, edge_slots, edge_stream, sl_phi,
  * mac_boxes, skip_marked_rows, tail_stream, diag_first, mac_noop_host, mac_face_sl,
- * mac_m2_bound, diag_seg, sl_zero_flags, dct_sym (read when the context's DCT
+ * mac_m2_bound, diag_seg, sl_zero_flags, macp_fused (rmt_mac_per_steps' explicit step: the
+ * predictor and the divergence in one kernel, same bits), dct_sym (read when the context's DCT
  * plan is made, at its first solve; it chooses another FFT of the same DCT-I, equal to
  * rounding, not bit for bit), and the test-only test_delay_geo / test_nowait_drop (a slab's
  * early geometry delayed; a dropped geometry not waited for).  Set them before creating a sim or slab on the context (sim_hiprio is read
@@ -535,6 +536,45 @@ int rmt_mac_sim_field(rmt_mac_sim *sim, int field, int disc, double **dev_ptr);
 int rmt_mac_sim_step(rmt_mac_sim *sim, int nsteps, double t_end);
 int rmt_mac_sim_diagnostics(rmt_mac_sim *sim, rmt_mac_diag *out, int max_records,
                             int *n_records);
+
+/* ---- periodic MAC tier (macper.hip): mac.py:445-540, 636-650 -----------------------
+ * ctx created for (ny, nx); u (x-faces), v (y-faces) and p (centres) are all (ny, nx) planes
+ * and every index wraps (np.roll); ny, nx >= 2, rectangular and odd extents allowed.
+ * The scalars a caller of the reference forms in Python come in formed: dx2 = dx**2,
+ * dy2 = dy**2, twodx = 2*dx, twody = 2*dy, coef = dt*nu, rho_dt = rho/dt, dt_rho = dt/rho.
+ * lx (nx) / ly (ny): HOST per-axis eigenvalues, symbol = lx[None,:] + ly[:,None] (one
+ * rounded add), applied on the ny x (nx/2+1) half-spectrum of a rocFFT D2Z / Z2D pair. */
+int rmt_mac_per_divergence(rmt_ctx *ctx, const double *u, const double *v, double dx, double dy,
+                           double *out);                                  /* mac.py:449-450 */
+/* gu or gv may be NULL */
+int rmt_mac_per_gradient_p(rmt_ctx *ctx, const double *p, double dx, double dy, double *gu,
+                           double *gv);                                   /* mac.py:453-458 */
+int rmt_mac_per_predictor(rmt_ctx *ctx, const double *u, const double *v, double nu, double dx2,
+                          double dy2, double twodx, double twody, double dt, double *u_star,
+                          double *v_star);                                /* mac.py:636-650 */
+int rmt_mac_per_predictor_imex(rmt_ctx *ctx, const double *u, const double *v, double twodx,
+                               double twody, double dt, double coef, const double *lx,
+                               const double *ly, double *u_star,
+                               double *v_star);                           /* mac.py:521-540 */
+/* mode 0: out = ifft(fft(rhs) / symbol), (0,0) zeroed (solve_poisson_periodic, mac.py:470-473);
+ * mode 1: out = ifft(fft(rhs) / (1 - coef * symbol)) (solve_helmholtz_periodic, :512-518).
+ * out may be rhs. */
+int rmt_mac_per_solve(rmt_ctx *ctx, const double *rhs, int mode, double coef, const double *lx,
+                      const double *ly, double *out);
+int rmt_mac_per_project(rmt_ctx *ctx, const double *u_star, const double *v_star, double dx,
+                        double dy, double rho_dt, double dt_rho, const double *lx,
+                        const double *ly, double *u, double *v,
+                        double *phi);                                     /* mac.py:476-480 */
+/* nsteps of predictor (imex 0: rmt_mac_per_predictor, 1: rmt_mac_per_predictor_imex) +
+ * projection on the device planes u, v in place, the loop of
+ * benchmarks/mac_taylor_green_convergence.py:59-66; no host round trip inside, workspace
+ * from the context.  p (may be NULL): the last projection's phi.  Option macp_fused
+ * (RMT_MACP_FUSED) picks the explicit step's fused predictor + divergence kernel; the
+ * results are the same bits as the separate entry points composed. */
+int rmt_mac_per_steps(rmt_ctx *ctx, double *u, double *v, double nu, double dx, double dy,
+                      double dx2, double dy2, double twodx, double twody, double dt, double coef,
+                      double rho_dt, double dt_rho, const double *lx, const double *ly, int imex,
+                      int nsteps, double *p);
 
 /* The MAC step decomposed into row slabs (config 5 on several GPUs).
  * No reference interface: pyRMT runs mac_multi_disc_lid.py:62-98 in one process.  Slab

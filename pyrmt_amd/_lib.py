@@ -200,6 +200,15 @@ SIGNATURES = {
     "rmt_mac_sim_field": (_I, [_P, _I, _I, ctypes.POINTER(_P)]),
     "rmt_mac_sim_step": (_I, [_P, _I, _D]),
     "rmt_mac_sim_diagnostics": (_I, [_P, ctypes.POINTER(rmt_mac_diag), _I, ctypes.POINTER(_I)]),
+    # periodic MAC tier (mac.py, macper.hip)
+    "rmt_mac_per_divergence": (_I, [_P, _P, _P, _D, _D, _P]),
+    "rmt_mac_per_gradient_p": (_I, [_P, _P, _D, _D, _P, _P]),
+    "rmt_mac_per_predictor": (_I, [_P, _P, _P, _D, _D, _D, _D, _D, _D, _P, _P]),
+    "rmt_mac_per_predictor_imex": (_I, [_P, _P, _P, _D, _D, _D, _D, _P, _P, _P, _P]),
+    "rmt_mac_per_solve": (_I, [_P, _P, _I, _D, _P, _P, _P]),
+    "rmt_mac_per_project": (_I, [_P, _P, _P, _D, _D, _D, _D, _P, _P, _P, _P, _P]),
+    "rmt_mac_per_steps": (_I, [_P, _P, _P, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _P, _P,
+                               _I, _I, _P]),
 }
 
 _lib = None

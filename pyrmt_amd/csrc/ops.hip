@@ -49,6 +49,7 @@ static const struct { const char *name, *env; int rmt_opts::*f; } kOpts[] = {
     {"diag_seg", "RMT_DIAG_SEG", &rmt_opts::diag_seg},
     {"sl_zero_flags", "RMT_SL_ZERO_FLAGS", &rmt_opts::sl_zero_flags},
     {"dct_sym", "RMT_DCT_SYM", &rmt_opts::dct_sym},
+    {"macp_fused", "RMT_MACP_FUSED", &rmt_opts::macp_fused},
 };
 int g_list_blocks = getenv("RMT_LIST_BLOCKS") ? std::max(1, atoi(getenv("RMT_LIST_BLOCKS")))
                                                 : LIST_BLOCKS;
@@ -876,6 +877,7 @@ int rmt_ctx_destroy(rmt_ctx *ctx) {
     if (ctx->dct) dct_destroy(ctx->dct);
     if (ctx->dct2) dct2_destroy(ctx->dct2);
     if (ctx->per) per_destroy(ctx->per);
+    if (ctx->macper) macper_destroy(ctx->macper);
     for (auto es : ctx->edge_sts)
         if (es) (void)hipStreamSynchronize(es);
     for (auto &e : ctx->edge)

@@ -70,6 +70,7 @@ void set_error(const std::string &msg);
 struct DctPlan;   // dct1.hip (DCT-I, collocated grid)
 struct Dct2Plan;  // dct2.hip (DCT-II, MAC grid)
 struct PerPlan;   // periodic.hip (reduced-grid 2D FFT)
+struct MacPerPlan;   // macper.hip (periodic MAC grid, 2D FFT)
 
 }  // namespace rmt
 
@@ -118,6 +119,10 @@ struct rmt_opts {
                               // coprime radices 3 .. 13 runs on half the row (k_dct1s; 0: k_dct1)
     int sl_zero_flags = 1;    // RMT_SL_ZERO_FLAGS: the side SL pass skips the loads and stores of
                               // tiles whose map stays +0.0 (zero-tile flags, k_sim_sl_t)
+    int macp_fused = 0;       // RMT_MACP_FUSED: the periodic MAC loop's explicit step computes the
+                              // predictor and the scaled divergence in one tiled kernel
+                              // (k_macp_predict_div; 0: k_macp_predict, k_macp_div), same bits;
+                              // 6 % faster at N = 4096, not at 1024
 };
 
 #define RMT_EDGE_PRIOS 2   // edge-tile streams kept, one per priority (momentum.hip edge_stream)
@@ -161,6 +166,7 @@ struct rmt_ctx {
     hipEvent_t edge_ev[9] = {};
     void *imex[2] = {nullptr, nullptr};   // imex.hip: the DST preconditioner plans (u, v)
     rmt_opts opt;   // implementation switches (above)
+    rmt::MacPerPlan *macper = nullptr;   // macper.hip: the periodic MAC tier's FFT plans
 };
 static_assert(sizeof(((rmt_ctx *)nullptr)->edge) / sizeof(rmt_ctx::EdgeTiles) == RMT_EDGE_SLOTS, "edge slots");
 
@@ -769,6 +775,7 @@ int dct2_pass(rmt_ctx *ctx, int mode, int axis, const double *src, double *dst, 
               int row0, const double *mroot = nullptr, double mcount = 1.0);
 void dct2_destroy(Dct2Plan *P);
 void per_destroy(PerPlan *P);
+void macper_destroy(MacPerPlan *P);
 void dct_destroy(DctPlan *);
 
 // ------------------------------------------------------------------ extrapolate --

@@ -5,6 +5,8 @@ Same names, arguments and return values as the reference module (mac.py:22-139,
 Layout as the reference: p / phi (Ny, Nx) cell centres, u (Ny, Nx+1) x-faces,
 v (Ny+1, Nx) y-faces (square grids: Nx == Ny).  ``MacMultiDisc`` is the device-resident
 loop body of benchmarks/mac_multi_disc_lid.py:36-98 (K soft discs with pair contact).
+The periodic tier (mac.py:445-540, 636-650; rmt_mac_per_*) keeps u, v and p all (Ny, Nx);
+``MacTaylorGreen`` / ``taylor_green_run_one`` are benchmarks/mac_taylor_green_convergence.py.
 """
 import ctypes
 import math
@@ -246,6 +248,260 @@ def contact_stress(phi_a, phi_b, eta, Gsum, eps, dx, dy):
     L.check(L.lib().rmt_mac_contact_stress(_ctx(a.shape[0]), _p(a), _p(b), eta, Gsum, eps, dx,
                                            dy, *map(_p, out)), "contact_stress")
     return tuple(io.out(t) for t in out)
+
+
+# ------------------------------------------------------------------ periodic tier ----
+# mac.py:445-540, 636-650 through macper.hip: u (x-faces), v (y-faces) and p (centres) are all
+# (Ny, Nx) planes and every index wraps.  The stencil operators are bit-exact; the solves go
+# through rocFFT on the half-spectrum (the reference: numpy.fft), equal to rounding.  Not
+# covered: momentum_predictor_periodic_semilag / _interp_per (grid-wrap cubic splines),
+# momentum_predictor_periodic_imex_elastic, momentum_predictor_freeslip,
+# advect_xi_conservative, interfacial_force_faces.
+def _pctx(shape):
+    return ctx_for(shape[0], shape[1]).bind()
+
+
+def _hp(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def divergence_per(u, v, dx, dy):
+    """mac.py:449-450."""
+    io = _IO(u, v); u = io.dev(u); v = io.dev(v)
+    out = io.empty(u.shape)
+    L.check(L.lib().rmt_mac_per_divergence(_pctx(u.shape), _p(u), _p(v), float(dx), float(dy),
+                                           _p(out)), "divergence_per")
+    return io.out(out)
+
+
+def grad_p_u_per(p, dx):
+    """mac.py:453-454."""
+    io = _IO(p); p = io.dev(p)
+    g = io.empty(p.shape)
+    L.check(L.lib().rmt_mac_per_gradient_p(_pctx(p.shape), _p(p), float(dx), float(dx), _p(g),
+                                           None), "grad_p_u_per")
+    return io.out(g)
+
+
+def grad_p_v_per(p, dy):
+    """mac.py:457-458."""
+    io = _IO(p); p = io.dev(p)
+    g = io.empty(p.shape)
+    L.check(L.lib().rmt_mac_per_gradient_p(_pctx(p.shape), _p(p), float(dy), float(dy), None,
+                                           _p(g)), "grad_p_v_per")
+    return io.out(g)
+
+
+def _per_axis(n, h):
+    return -4.0 * np.sin(np.pi * np.arange(n) / n) ** 2 / h**2
+
+
+def poisson_eigs_periodic(Nx, Ny, dx, dy):
+    """mac.py:461-467 (setup, host): FFT symbol of the roll stencil, (0,0) pinned to 1."""
+    eig = (_per_axis(Nx, dx)[np.newaxis, :] + _per_axis(Ny, dy)[:, np.newaxis]).copy()
+    eig[0, 0] = 1.0
+    return eig
+
+
+def lap_eigs_periodic(Nx, Ny, dx, dy):
+    """mac.py:501-509 (setup, host): the same symbol, not pinned ((0,0) is -0.0)."""
+    return _per_axis(Nx, dx)[np.newaxis, :] + _per_axis(Ny, dy)[:, np.newaxis]
+
+
+def _axis_eigs_per(eig, pinned):
+    """Per-axis vectors (lx, ly) of a periodic symbol table: row 0 and column 0 (the
+    reference's lam[0] is -0.0, so eig[0, k] == lx[k] exactly).  pinned: the Poisson table,
+    whose (0,0) entry is the pin (1.0) and is ignored, as the solve zeroes that mode; else the
+    Laplacian table, checked at (0,0) too.  The table must equal lx[None, :] + ly[:, None] bit
+    for bit, and each axis must be even in the wavenumber to rounding (the solve works on the
+    half-spectrum); anything else raises NotImplementedError -- there is no host fallback."""
+    if hasattr(eig, "cpu"):
+        eig = eig.cpu().numpy()
+    eig = np.ascontiguousarray(eig, dtype=np.float64)
+    if eig.ndim != 2 or min(eig.shape) < 2:
+        raise NotImplementedError("periodic symbol: a (Ny, Nx) table with Ny, Nx >= 2")
+    lx = eig[0, :].copy(); ly = eig[:, 0].copy()
+    ly[0] = -0.0
+    if pinned:
+        lx[0] = -0.0
+    chk = np.ascontiguousarray(lx[np.newaxis, :] + ly[:, np.newaxis])
+    if pinned:
+        chk[0, 0] = eig[0, 0]
+    if not np.array_equal(chk.view(np.int64), eig.view(np.int64)):
+        raise NotImplementedError("eig is not a separable per-axis symbol (periodic FFT solve)")
+    for lam in (lx, ly):
+        if np.abs(lam[1:] - lam[1:][::-1]).max() > 1e-12 * np.abs(lam).max():
+            raise NotImplementedError("eig is not even in the wavenumber (half-spectrum solve)")
+    return lx, ly
+
+
+def _solve_per(rhs, lx, ly, mode, coef, what):
+    io = _IO(rhs); r = io.dev(rhs)
+    if tuple(r.shape) != (ly.size, lx.size):
+        raise ValueError(f"{what}: rhs {tuple(r.shape)} against a {(ly.size, lx.size)} symbol")
+    out = io.empty(r.shape)
+    L.check(L.lib().rmt_mac_per_solve(_pctx(r.shape), _p(r), mode, float(coef), _hp(lx), _hp(ly),
+                                      _p(out)), what)
+    return io.out(out)
+
+
+def solve_poisson_periodic(rhs, eig):
+    """mac.py:470-473."""
+    lx, ly = _axis_eigs_per(eig, True)
+    return _solve_per(rhs, lx, ly, 0, 0.0, "solve_poisson_periodic")
+
+
+def solve_helmholtz_periodic(rhs, lap_eig, coef):
+    """mac.py:512-518: (I - coef Lap) x = rhs."""
+    lx, ly = _axis_eigs_per(lap_eig, False)
+    return _solve_per(rhs, lx, ly, 1, coef, "solve_helmholtz_periodic")
+
+
+def project_per(u_star, v_star, dx, dy, dt, rho, eig):
+    """mac.py:476-480: returns (u, v, phi)."""
+    lx, ly = _axis_eigs_per(eig, True)
+    io = _IO(u_star, v_star); us = io.dev(u_star); vs = io.dev(v_star)
+    if tuple(us.shape) != (ly.size, lx.size):
+        raise ValueError("project_per: the fields and eig differ in shape")
+    u = io.empty(us.shape); v = io.empty(us.shape); phi = io.empty(us.shape)
+    L.check(L.lib().rmt_mac_per_project(_pctx(us.shape), _p(us), _p(vs), float(dx), float(dy),
+                                        float(rho / dt), float(dt / rho), _hp(lx), _hp(ly),
+                                        _p(u), _p(v), _p(phi)), "project_per")
+    return io.out(u), io.out(v), io.out(phi)
+
+
+def momentum_predictor_periodic(u, v, nu, dx, dy, dt):
+    """mac.py:636-650: forward Euler, central advection + diffusion.  dx**2, 2*dx are formed
+    here, on the caller's scalar types, as the reference forms them."""
+    io = _IO(u, v); ud = io.dev(u); vd = io.dev(v)
+    us = io.empty(ud.shape); vs = io.empty(ud.shape)
+    L.check(L.lib().rmt_mac_per_predictor(_pctx(ud.shape), _p(ud), _p(vd), float(nu),
+                                          float(dx**2), float(dy**2), float(2 * dx),
+                                          float(2 * dy), float(dt), _p(us), _p(vs)),
+            "momentum_predictor_periodic")
+    return io.out(us), io.out(vs)
+
+
+def momentum_predictor_periodic_imex(u, v, nu, dx, dy, dt, lap_eig):
+    """mac.py:521-540: explicit central advection, backward-Euler viscosity by two FFT
+    Helmholtz solves."""
+    lx, ly = _axis_eigs_per(lap_eig, False)
+    io = _IO(u, v); ud = io.dev(u); vd = io.dev(v)
+    if tuple(ud.shape) != (ly.size, lx.size):
+        raise ValueError("momentum_predictor_periodic_imex: the fields and lap_eig differ in shape")
+    us = io.empty(ud.shape); vs = io.empty(ud.shape)
+    L.check(L.lib().rmt_mac_per_predictor_imex(_pctx(ud.shape), _p(ud), _p(vd), float(2 * dx),
+                                               float(2 * dy), float(dt), float(dt * nu),
+                                               _hp(lx), _hp(ly), _p(us), _p(vs)),
+            "momentum_predictor_periodic_imex")
+    return io.out(us), io.out(vs)
+
+
+_PER_INTEGRATORS = {"explicit": "explicit", "exp": "explicit", "forward-euler": "explicit",
+                    "imex": "imex", "imex-visc": "imex", "implicit-viscosity": "imex",
+                    "semi-implicit": "imex"}
+_ELASTIC_INTEGRATORS = ("imex-elastic", "elastic", "implicit-elastic")
+
+
+def _resolve_periodic_integrator(integrator=None, implicit_visc=False):
+    """The integrator of mac_taylor_green_convergence.py:47-52 (resolve_integrator with
+    supports_elastic=False, mac.py:46-78): "explicit" or "imex" from None + the legacy
+    boolean or one of the reference's aliases."""
+    if integrator is None:
+        return "imex" if implicit_visc else "explicit"
+    key = str(integrator).lower().replace("_", "-").strip()
+    if key == "imex-sl":
+        raise NotImplementedError("integrator 'imex-sl' (semi-Lagrangian periodic predictor, "
+                                  "mac.py:587-633) is not built")
+    if key in _ELASTIC_INTEGRATORS:
+        raise ValueError("integrator='imex-elastic' is not available for this driver "
+                         "(no solid-stress force path); use 'explicit' or 'imex'")
+    if key not in _PER_INTEGRATORS:
+        raise ValueError(f"unknown integrator {integrator!r}; choose from "
+                         "('explicit', 'imex', 'imex-elastic')")
+    return _PER_INTEGRATORS[key]
+
+
+class MacPeriodic:
+    """The loop body of mac_taylor_green_convergence.py:59-66 on the GPU (rmt_mac_per_steps):
+    u, v (and the last projection's phi, p) stay in HBM, a call of step(n) runs n predictor +
+    projection steps at the fixed dt with no host round trip.  options: implementation
+    switches of a context of its own (macp_fused)."""
+
+    def __init__(self, ny, nx, dx, dy, nu, dt, rho=1.0, integrator=None, options=None):
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("pyrmt_amd needs a visible MI355X")
+        self.integrator = _resolve_periodic_integrator(integrator)
+        self.torch, self.shape = torch, (int(ny), int(nx))
+        self.dx, self.dy, self.nu, self.dt, self.rho = dx, dy, nu, dt, rho
+        if options:
+            from .functions import _Ctx
+            self.ctx = _Ctx(self.shape[0], self.shape[1], torch.cuda.current_device())
+            for k, val in options.items():
+                self.ctx.set_option(k, val)
+        else:
+            self.ctx = ctx_for(*self.shape)
+        self.lx, self.ly = _axis_eigs_per(lap_eigs_periodic(nx, ny, dx, dy), False)
+        self.u, self.v, self.p = (torch.zeros(self.shape, dtype=torch.float64, device="cuda")
+                                  for _ in range(3))
+        self.nsteps = 0
+
+    def set(self, u, v):
+        io = _IO(u, v)
+        self.u.copy_(io.dev(u)); self.v.copy_(io.dev(v))
+
+    def step(self, nsteps=1):
+        dx, dy, dt = self.dx, self.dy, self.dt
+        L.check(L.lib().rmt_mac_per_steps(
+            self.ctx.bind(), _p(self.u), _p(self.v), float(self.nu), float(dx), float(dy),
+            float(dx**2), float(dy**2), float(2 * dx), float(2 * dy), float(dt),
+            float(dt * self.nu), float(self.rho / dt), float(dt / self.rho), _hp(self.lx),
+            _hp(self.ly), int(self.integrator == "imex"), int(nsteps), _p(self.p)),
+            "rmt_mac_per_steps")
+        self.nsteps += int(nsteps)
+
+    def get(self, name):
+        self.torch.cuda.synchronize()
+        return getattr(self, name).cpu().numpy()
+
+
+def _tg_faces(N):
+    """mac_taylor_green_convergence.py:24-31: face coordinates on [0, 2 pi]^2."""
+    dx = 2 * np.pi / N
+    xf = np.arange(N) * dx; xc = (np.arange(N) + 0.5) * dx
+    Xu, Yu = np.meshgrid(xf, xc)
+    Xv, Yv = np.meshgrid(xc, xf)
+    return dx, Xu, Yu, Xv, Yv
+
+
+def tg_exact(Xu, Yu, Xv, Yv, nu, t):
+    """mac_taylor_green_convergence.py:34-36 (host): the decaying Taylor-Green vortex."""
+    e = np.exp(-2 * nu * t)
+    return -np.cos(Xu) * np.sin(Yu) * e, np.sin(Xv) * np.cos(Yv) * e
+
+
+class MacTaylorGreen(MacPeriodic):
+    """The decaying Taylor-Green vortex on [0, 2 pi]^2 at N x N, rho = 1."""
+
+    def __init__(self, N, nu, dt, integrator=None, options=None):
+        dx, *self.faces = _tg_faces(N)
+        super().__init__(N, N, dx, dx, nu, dt, 1.0, integrator, options)
+        self.set(*tg_exact(*self.faces, nu, 0.0))
+
+    def exact(self):
+        return tg_exact(*self.faces, self.nu, self.nsteps * self.dt)
+
+
+def taylor_green_run_one(N, nu=0.05, T=0.2, dt=2e-4, implicit_visc=False, integrator=None):
+    """mac_taylor_green_convergence.py:39-70 (run_one): integrate to T, return (L2 error of u
+    against the exact solution, max|div|)."""
+    sim = MacTaylorGreen(N, nu, dt, _resolve_periodic_integrator(integrator, implicit_visc))
+    sim.step(int(round(T / dt)))
+    ue, _ = sim.exact()
+    erru = np.sqrt(np.mean((sim.get("u") - ue) ** 2))
+    divmax = float(divergence_per(sim.u, sim.v, sim.dx, sim.dx).abs().max())
+    return erru, divmax
 
 
 # ------------------------------------------------------------------ config 5 loop --
