@@ -62,7 +62,10 @@ const char *rmt_last_error(void);
 int rmt_version(void);
 
 /* Context: one device, one stream, one grid shape.  stream may be NULL (null stream)
- * or a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream). */
+ * or a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream).  ny, nx >= 2; the
+ * collocated operators (5-point-wide stencils) are only defined on ny, nx >= 5 -- a smaller
+ * context serves only the DCT-II Neumann solve (rmt_mac_solve_poisson_neumann,
+ * rmt_selftest_dct2_rows) and, square from 3 x 3, the periodic FFT solve. */
 int rmt_ctx_create(int ny, int nx, int device, void *stream, rmt_ctx **out);
 int rmt_ctx_set_stream(rmt_ctx *ctx, void *stream);
 int rmt_ctx_destroy(rmt_ctx *ctx);
@@ -245,6 +248,15 @@ int rmt_solve_poisson_dct(rmt_ctx *ctx, const double *rhs, double dx, double dy,
 int rmt_selftest_dct_rows(rmt_ctx *ctx, const double *src, double dx, double dy, double scale,
                           double *dst, double *rs, double *rs_ref,
                           const unsigned char *rowmark, int unmarked);
+/* Test hook (no reference counterpart): one row pass of the DCT-II Neumann solve (mac.py:118-123)
+ * under the plan of this context's (ny, nx) and (dx, dy).  axis 0: rows of length nx, 1: rows
+ * of length ny; src, dst (device, nrows rows of that length; may alias).  mode 0: dst = the
+ * unnormalised DCT-II 2 sum x cos of every row (mroot nullable: of x - mroot[0] / mcount);
+ * mode 2: its inverse; mode 1 (axis 1): forward, row r / (lamx[row0 + r] + lamy[k]) with the
+ * (row0 + r = 0, k = 0) entry zeroed, inverse.  Rows >= nrows of dst are left as they are. */
+int rmt_selftest_dct2_rows(rmt_ctx *ctx, int mode, int axis, const double *src, int nrows,
+                           int row0, const double *mroot, double mcount, double dx, double dy,
+                           double *dst);
 /* functions.py:1255-1364 pressure_projection_amg, Neumann branch, constant density rho
  * (variable density: rmt_pressure_projection_variable).  p_prev may be NULL. */
 int rmt_pressure_projection(rmt_ctx *ctx, const double *a_star, const double *b_star,

@@ -111,6 +111,7 @@ SIGNATURES = {
     "rmt_pressure_gradient": (_I, [_P, _P, _D, _D, _P, _P]),
     "rmt_solve_poisson_dct": (_I, [_P, _P, _D, _D, _P]),
     "rmt_selftest_dct_rows": (_I, [_P, _P, _D, _D, _D, _P, _P, _P, _P, _I]),
+    "rmt_selftest_dct2_rows": (_I, [_P, _I, _I, _P, _I, _I, _P, _D, _D, _D, _P]),
     "rmt_pressure_projection": (_I, [_P, _P, _P, _D, _D, _D, _D, _I, _D, _P, _P, _P, _P]),
     "rmt_pressure_projection_variable": (_I, [_P, _P, _P, _D, _D, _D, _P, _I, _D, _P, _D, _I,
                                               _P, _P, _P, ctypes.POINTER(_I)]),

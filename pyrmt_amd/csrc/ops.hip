@@ -811,7 +811,8 @@ const char *rmt_last_error(void) { return g_err.c_str(); }
 int rmt_version(void) { return 1; }
 
 int rmt_ctx_create(int ny, int nx, int device, void *stream, rmt_ctx **out) {
-    RMT_CHECK(out && ny >= 5 && nx >= 5, RMT_EINVAL, "rmt_ctx_create: need ny, nx >= 5");
+    // 2: the shortest DCT-II axis (mac.py:118-123); the collocated stencils need 5 (rmt.h)
+    RMT_CHECK(out && ny >= 2 && nx >= 2, RMT_EINVAL, "rmt_ctx_create: need ny, nx >= 2");
     RMT_HIP(hipSetDevice(device));
     rmt_ctx *c = new rmt_ctx;
     c->ny = ny; c->nx = nx; c->device = device; c->stream = (hipStream_t)stream;
@@ -1068,6 +1069,19 @@ int rmt_selftest_dct_rows(rmt_ctx *ctx, const double *src, double dx, double dy,
         RMT_LAUNCHED();
     }
     return RMT_OK;
+}
+int rmt_selftest_dct2_rows(rmt_ctx *ctx, int mode, int axis, const double *src, int nrows,
+                           int row0, const double *mroot, double mcount, double dx, double dy,
+                           double *dst) {
+    RMT_CHECK(ctx && src && dst, RMT_EINVAL, "null argument");
+    RMT_CHECK(axis == 0 || axis == 1, RMT_EINVAL, "selftest_dct2_rows: axis 0 or 1");
+    RMT_CHECK(nrows >= 1 && nrows <= (axis == 0 ? ctx->ny : ctx->nx), RMT_EINVAL,
+              "selftest_dct2_rows: nrows out of range");
+    // mode 1 divides row r by lamx[row0 + r] + lamy[k]: the rows are x-frequencies
+    RMT_CHECK(mode != 1 || (axis == 1 && row0 >= 0 && row0 + nrows <= ctx->nx), RMT_EINVAL,
+              "selftest_dct2_rows: mode 1 runs along axis 1 on rows row0 .. row0 + nrows <= nx");
+    RMT_TRY(dct2_plan(ctx, ctx->ny, ctx->nx, dx, dy));
+    return dct2_pass(ctx, mode, axis, src, dst, nrows, row0, mroot, mcount);
 }
 int rmt_pressure_projection(rmt_ctx *ctx, const double *a_star, const double *b_star,
                             double dx, double dy, double dt, double rho, int bc_kind,

@@ -25,7 +25,11 @@ def _torch():
 
 
 class _Ctx:
-    def __init__(self, ny, nx, device):
+    def __init__(self, ny, nx, device, stencils=True):
+        """stencils=False: a context for the DCT-II Neumann solve (axes from 2) or the periodic
+        FFT solve (from 3 x 3) alone; every array wrapper keeps the stencils' ny, nx >= 5."""
+        if stencils and (ny < 5 or nx < 5):
+            raise ValueError("rmt_ctx_create: need ny, nx >= 5")
         self.ny, self.nx, self.device = ny, nx, device
         h = ctypes.c_void_p()
         L.check(L.lib().rmt_ctx_create(ny, nx, device, None, ctypes.byref(h)), "rmt_ctx_create")

@@ -3,8 +3,9 @@
 Same names, arguments and return values as the reference module (mac.py:22-139,
 196-232, 729-749); the arrays go through librmt's HIP kernels (include/rmt.h, rmt_mac_*).
 Layout as the reference: p / phi (Ny, Nx) cell centres, u (Ny, Nx+1) x-faces,
-v (Ny+1, Nx) y-faces (square grids: Nx == Ny).  ``MacMultiDisc`` is the device-resident
-loop body of benchmarks/mac_multi_disc_lid.py:36-98 (K soft discs with pair contact).
+v (Ny+1, Nx) y-faces (square grids: Nx == Ny, checked by _lid_n; solve_poisson_neumann alone
+takes Ny != Nx).  ``MacMultiDisc`` is the device-resident loop body of
+benchmarks/mac_multi_disc_lid.py:36-98 (K soft discs with pair contact).
 The periodic tier (mac.py:445-540, 636-650; rmt_mac_per_*) keeps u, v and p all (Ny, Nx);
 ``MacTaylorGreen`` / ``taylor_green_run_one`` are benchmarks/mac_taylor_green_convergence.py.
 """
@@ -49,18 +50,39 @@ def _ctx(N):
     return ctx_for(N, N).bind()
 
 
+def _lid_n(what, u=None, v=None, fu=None, fv=None, **cells):
+    """N of the square grid the lid-tier arrays live on: u, fu (N, N+1) x-faces, v, fv
+    (N+1, N) y-faces, every keyword field (N, N) cell centres.  The kernels behind _ctx(N) are
+    square-only and index their arrays by N alone, so anything else (Ny != Nx included, which
+    the reference accepts) raises NotImplementedError here, before any library call."""
+    arrays = [("u", u, 0, 1), ("v", v, 1, 0), ("fu", fu, 0, 1), ("fv", fv, 1, 0)]
+    arrays += [(k, a, 0, 0) for k, a in cells.items()]
+    shapes = {k: tuple(np.shape(a)) for k, a, _, _ in arrays if a is not None}
+    N = None
+    for k, a, ey, ex in arrays:
+        if a is None:
+            continue
+        if N is None and len(shapes[k]) == 2:
+            N = shapes[k][0] - ey
+        if N is None or shapes[k] != (N + ey, N + ex):
+            raise NotImplementedError(
+                f"{what}: the lid-tier MAC kernels are square-only (u (N, N+1), v (N+1, N), "
+                f"cell fields (N, N)); got {shapes}")
+    return N
+
+
 def divergence(u, v, dx, dy):
     """mac.py:81-84."""
+    N = _lid_n("divergence", u, v)
     io = _IO(u, v); u = io.dev(u); v = io.dev(v)
-    N = u.shape[0]
     out = io.empty((N, N))
     L.check(L.lib().rmt_mac_divergence(_ctx(N), _p(u), _p(v), dx, dy, _p(out)), "divergence")
     return io.out(out)
 
 
-def _gradients(p, dx, dy):
+def _gradients(what, p, dx, dy):
+    N = _lid_n(what, p=p)
     io = _IO(p); p = io.dev(p)
-    N = p.shape[0]
     gu = io.empty((N, N + 1)); gv = io.empty((N + 1, N))
     L.check(L.lib().rmt_mac_gradient_p(_ctx(N), _p(p), dx, dy, _p(gu), _p(gv)), "gradient_p")
     return io, gu, gv
@@ -68,33 +90,38 @@ def _gradients(p, dx, dy):
 
 def gradient_p_u(p, dx):
     """mac.py:87-93."""
-    io, gu, _ = _gradients(p, dx, dx)
+    io, gu, _ = _gradients("gradient_p_u", p, dx, dx)
     return io.out(gu)
 
 
 def gradient_p_v(p, dy):
     """mac.py:96-101."""
-    io, _, gv = _gradients(p, dy, dy)
+    io, _, gv = _gradients("gradient_p_v", p, dy, dy)
     return io.out(gv)
 
 
 def solve_poisson_neumann(rhs, eig):
-    """mac.py:118-123 (orthonormal DCT-II both ways, constant mode zeroed)."""
+    """mac.py:118-123 (orthonormal DCT-II both ways, constant mode zeroed).  (Ny, Nx) may
+    differ, as in the reference: the solve binds a context of that shape."""
+    shp = tuple(np.shape(rhs))
+    if len(shp) != 2 or tuple(np.shape(eig)) != shp:
+        raise NotImplementedError(f"solve_poisson_neumann: rhs {shp} and eig "
+                                  f"{tuple(np.shape(eig))} must be one (Ny, Nx) shape")
     lx, ly = _axis_eigs(eig)
     io = _IO(rhs); r = io.dev(rhs)
-    N = r.shape[0]
-    out = io.empty((N, N))
+    Ny, Nx = shp
+    out = io.empty(shp)
     L.check(L.lib().rmt_mac_solve_poisson_neumann(
-        _ctx(N), _p(r), 1.0 / N, 1.0 / N, lx.ctypes.data_as(ctypes.c_void_p),
+        ctx_for(Ny, Nx).bind(), _p(r), 1.0 / Nx, 1.0 / Ny, lx.ctypes.data_as(ctypes.c_void_p),
         ly.ctypes.data_as(ctypes.c_void_p), _p(out)), "solve_poisson_neumann")
     return io.out(out)
 
 
 def project(u_star, v_star, dx, dy, dt, rho, eig):
     """mac.py:126-139: returns (u, v, phi)."""
+    N = _lid_n("project", u_star, v_star, eig=eig)
     lx, ly = _axis_eigs(eig)
     io = _IO(u_star, v_star); us = io.dev(u_star); vs = io.dev(v_star)
-    N = us.shape[0]
     u = io.empty(us.shape); v = io.empty(vs.shape); phi = io.empty((N, N))
     L.check(L.lib().rmt_mac_project(_ctx(N), _p(us), _p(vs), dx, dy, dt, float(rho),
                                     lx.ctypes.data_as(ctypes.c_void_p),
@@ -107,10 +134,11 @@ def momentum_predictor(u, v, nu, dx, dy, dt, U_lid, fu=None, fv=None, rho=1.0):
     """mac.py:196-232."""
     if (fu is None) != (fv is None):
         raise NotImplementedError("momentum_predictor: give both face forces or neither")
+    N = _lid_n("momentum_predictor", u, v, fu, fv)
     io = _IO(u, v); ud = io.dev(u); vd = io.dev(v)
     fud, fvd = io.dev(fu), io.dev(fv)
     us = io.empty(ud.shape); vs = io.empty(vd.shape)
-    L.check(L.lib().rmt_mac_momentum_predictor(_ctx(ud.shape[0]), _p(ud), _p(vd), nu, dx, dy,
+    L.check(L.lib().rmt_mac_momentum_predictor(_ctx(N), _p(ud), _p(vd), nu, dx, dy,
                                                dt, U_lid, _p(fud), _p(fvd), float(rho), _p(us),
                                                _p(vs)), "momentum_predictor")
     return io.out(us), io.out(vs)
@@ -120,8 +148,8 @@ def momentum_predictor(u, v, nu, dx, dy, dt, U_lid, fu=None, fv=None, rho=1.0):
 # mac.py:243-442 through imex.hip: the homogeneous ghost-cell Laplacians,
 # CG / DST-preconditioned CG Helmholtz solves and the IMEX lid-cavity predictor.
 def _lap_hom(kind, f, dx, dy):
+    N = _lid_n("_lap_u_lid_hom", u=f) if kind == 0 else _lid_n("_lap_v_lid_hom", v=f)
     io = _IO(f); fd = io.dev(f)
-    N = fd.shape[0] if kind == 0 else fd.shape[1]
     out = io.empty((N, N - 1) if kind == 0 else (N - 1, N))
     L.check(L.lib().rmt_mac_lap_lid_hom(_ctx(N), kind, _p(fd), float(dx), float(dy), _p(out)),
             "_lap_lid_hom")
@@ -178,6 +206,9 @@ def _helmholtz_operator(apply_lap_hom, embed, shp):
 def _solve_helmholtz(rhs_int, kind, coef, dx, dy, rtol, maxiter, precond):
     io = _IO(rhs_int); b = io.dev(rhs_int)
     N = b.shape[0] if kind == 0 else b.shape[1]
+    if tuple(b.shape) != ((N, N - 1) if kind == 0 else (N - 1, N)):
+        raise NotImplementedError(f"helmholtz: the interior faces of a square grid, (N, N-1) "
+                                  f"for u or (N-1, N) for v; got {tuple(b.shape)}")
     x = io.empty(b.shape)
     it = ctypes.c_int(0)
     L.check(L.lib().rmt_mac_helmholtz(_ctx(N), kind, _p(b), float(coef), dx, dy, float(rtol),
@@ -209,12 +240,13 @@ def momentum_predictor_lid_imex(u, v, nu, dx, dy, dt, U_lid, fu=None, fv=None, r
                                 rtol=1e-8, cs2=0.0):
     """mac.py:319-369: explicit central advection + face forces, implicit (backward-Euler)
     viscosity (+ the trapezoidal elastic term, cs2 > 0) by DST-preconditioned CG."""
+    N = _lid_n("momentum_predictor_lid_imex", u, v, fu, fv)
     io = _IO(u, v); ud = io.dev(u); vd = io.dev(v)
     fud, fvd = io.dev(fu), io.dev(fv)
     us = io.empty(ud.shape); vs = io.empty(vd.shape)
     it = (ctypes.c_int * 2)()
     L.check(L.lib().rmt_mac_momentum_predictor_lid_imex(
-        _ctx(ud.shape[0]), _p(ud), _p(vd), float(nu), float(dx), float(dy), float(dt),
+        _ctx(N), _p(ud), _p(vd), float(nu), float(dx), float(dy), float(dt),
         float(U_lid), _p(fud), _p(fvd), float(rho), float(rtol), float(cs2), _p(us), _p(vs),
         ctypes.cast(it, ctypes.c_void_p)), "momentum_predictor_lid_imex")
     return io.out(us), io.out(vs)
@@ -226,6 +258,7 @@ def momentum_predictor_lid_semilag(u, v, nu, dx, dy, dt, U_lid, fu=None, fv=None
     CFL <= cfl_switch (mac.py:387-390), else the semi-Lagrangian midpoint backtrace through
     cubic-spline interpolation (map_coordinates order 3, 'nearest') and the same PCG
     viscosity solve."""
+    N = _lid_n("momentum_predictor_lid_semilag", u, v, fu, fv)
     io = _IO(u, v); ud = io.dev(u); vd = io.dev(v)
     cfl = dt * max(float(ud.abs().max()) / dx, float(vd.abs().max()) / dy)
     if cfl <= cfl_switch:
@@ -235,7 +268,7 @@ def momentum_predictor_lid_semilag(u, v, nu, dx, dy, dt, U_lid, fu=None, fv=None
     us = io.empty(ud.shape); vs = io.empty(vd.shape)
     it = (ctypes.c_int * 2)()
     L.check(L.lib().rmt_mac_momentum_predictor_lid_semilag(
-        _ctx(ud.shape[0]), _p(ud), _p(vd), float(nu), float(dx), float(dy), float(dt),
+        _ctx(N), _p(ud), _p(vd), float(nu), float(dx), float(dy), float(dt),
         float(U_lid), _p(fud), _p(fvd), float(rho), float(cs2), float(rtol), _p(us), _p(vs),
         ctypes.cast(it, ctypes.c_void_p)), "momentum_predictor_lid_semilag")
     return io.out(us), io.out(vs)
@@ -243,9 +276,10 @@ def momentum_predictor_lid_semilag(u, v, nu, dx, dy, dt, U_lid, fu=None, fv=None
 
 def contact_stress(phi_a, phi_b, eta, Gsum, eps, dx, dy):
     """mac.py:729-749: (txx, txy, tyy)."""
+    N = _lid_n("contact_stress", phi_a=phi_a, phi_b=phi_b)
     io = _IO(phi_a, phi_b); a = io.dev(phi_a); b = io.dev(phi_b)
     out = [io.empty(a.shape) for _ in range(3)]
-    L.check(L.lib().rmt_mac_contact_stress(_ctx(a.shape[0]), _p(a), _p(b), eta, Gsum, eps, dx,
+    L.check(L.lib().rmt_mac_contact_stress(_ctx(N), _p(a), _p(b), eta, Gsum, eps, dx,
                                            dy, *map(_p, out)), "contact_stress")
     return tuple(io.out(t) for t in out)
 

@@ -33,6 +33,37 @@ def test_periodic_fft_solve(gpu):
     assert np.max(np.abs((p - pt)[:-1, :-1])) < 1e-10
 
 
+@pytest.mark.parametrize("N", [3, 4, 5, 10, 34, 65, 130])
+def test_periodic_fft_solve_sizes(gpu, oracle, N):
+    """rmt_solve_poisson_fft at both parities of m = N - 1 (the Nyquist null mode exists only
+    for even m) against the oracle's numpy.fft solve on a random right-hand side, to this
+    file's 1e-12 of max|p_ref|.  N = 3: every mode is null and p_ref is identically zero, so
+    the bar is an absolute 1e-12 there.  The entry is bound directly: N < 5 is below what the
+    array wrappers' contexts take, and at N = 3 no grid spacing can be read back from an
+    all-null table."""
+    import ctypes
+    import torch
+    from pyrmt_amd import functions as F, _lib as L
+    dx, dy = 1.0 / (N - 1), 0.7 / (N - 1)
+    rhs = np.random.default_rng(N).standard_normal((N, N))
+    ref = oracle._solve_poisson_fft(rhs,
+                                    oracle._precompute_poisson_eigenvalues_periodic(N, N, dx, dy))
+    lx = np.ascontiguousarray(F._periodic_axis(N, dx))
+    ly = np.ascontiguousarray(F._periodic_axis(N, dy))
+    c = F._Ctx(N, N, torch.cuda.current_device(), stencils=False)
+    r = torch.from_numpy(rhs).cuda()
+    out = torch.empty_like(r)
+    L.check(L.lib().rmt_solve_poisson_fft(c.bind(), F._p(r), lx.ctypes.data_as(ctypes.c_void_p),
+                                          ly.ctypes.data_as(ctypes.c_void_p), F._p(out)),
+            "rmt_solve_poisson_fft")
+    sc = np.abs(ref).max()
+    if N == 3:
+        assert sc == 0.0
+    err = np.abs(out.cpu().numpy() - ref).max()
+    print(N, err, sc)
+    assert err <= 1e-12 * (sc if N > 3 else 1.0)
+
+
 def test_periodic_projection(gpu):
     from pyrmt_amd.bc import Periodic
 
