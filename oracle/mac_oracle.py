@@ -131,7 +131,8 @@ class MacMultiDisc:
     its own reference map advected on the cell-centre velocity, blended solid stress +
     pair contact stress -> face force, explicit MAC predictor, exact DCT-II projection."""
 
-    def __init__(self, N, n_discs=3, seed=3, U_lid=1.0, mu_s=0.3, mu_f=0.01, rho=1.0, eta=2.0):
+    def __init__(self, N, n_discs=3, seed=3, U_lid=1.0, mu_s=0.3, mu_f=0.01, rho=1.0, eta=2.0,
+                 specs=None):
         dx, dy = mac_grid(N, N)
         self.N, self.dx, self.dy = N, dx, dy
         xc = (np.arange(N) + 0.5) * dx
@@ -139,7 +140,8 @@ class MacMultiDisc:
         self.Xg, self.Yg = np.meshgrid(np.arange(N) * dx, np.arange(N) * dy)
         self.w_t, self.nu, self.eps = 2.0 * dx, mu_f / rho, 3.0 * dx
         self.U, self.mu_s, self.rho, self.eta = U_lid, mu_s, rho, eta
-        self.specs = place_discs(n_discs, seed)
+        # specs: explicit (R, cx, cy) per disc instead of the driver's random placement
+        self.specs = list(specs) if specs is not None else place_discs(n_discs, seed)
         self.refs = []
         for (R, cx, cy) in self.specs:
             phi = rebuild_phi_disc(self.Xc, self.Yc, cx, cy, R)

@@ -15,7 +15,8 @@
 
 namespace rmt {
 
-__device__ __forceinline__ int mk_src(int m, int n) { return m < n / 2 ? 2 * m : 2 * (n - 1 - m) + 1; }
+// (odd n: the even samples are one more than the odd ones, (n + 1) / 2 of them)
+__device__ __forceinline__ int mk_src(int m, int n) { return m < (n + 1) / 2 ? 2 * m : 2 * (n - 1 - m) + 1; }
 
 // factor(8192)'s plan: radices 2, 8, 8, 8, 8 (ascending), twiddle offsets 0, 1, 15, 127, 1023
 template <int NT>
@@ -174,10 +175,10 @@ int dct2_plan(rmt_ctx *ctx, int ny, int nx, double dx, double dy) {
     if (P) { dct2_destroy(P); ctx->dct2 = nullptr; }
     P = new Dct2Plan;
     P->ny = ny; P->nx = nx; P->dx = dx; P->dy = dy;
-    if ((nx & 1) || (ny & 1) || !factor(nx, P->radx, &P->npx) || !factor(ny, P->rady, &P->npy) ||
-        !lds_fits(nx) || !lds_fits(ny)) {
+    if (!factor(nx, P->radx, &P->npx) || !factor(ny, P->rady, &P->npy) || !lds_fits(nx) ||
+        !lds_fits(ny)) {
         delete P;
-        set_error("DCT-II solve: N must be even, <= 8192, and factor into radices <= 23");
+        set_error("DCT-II solve: N must be 2 .. 8192 and factor into radices <= 23");
         return RMT_ENOTSUP;
     }
     P->big = big_radix(P->radx, P->npx) || big_radix(P->rady, P->npy);

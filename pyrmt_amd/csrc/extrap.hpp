@@ -17,6 +17,10 @@ constexpr int CH_W = RMT_CH_W;      // chain workgroup waves (4 per SIMD)
 constexpr int CH_HDR = 24;          // record header, doubles
 constexpr int CH_TVS = 88;          // padded fold terms per sum (81 rounded up to 8)
 constexpr int CH_MAXREC = 8 * (CH_HDR + 6 * CH_TVS + 4 * 64);   // 6464 B (<= 64 sources)
+// what k_ex_chain stages of a record: five 16-byte pieces per lane (CH_LOAD).  A longer record
+// (4 nd + 6 npad > 616 doubles: a nearly full window with many same-call sources, which needs
+// known cells on both sides of the band) sends the call to the fallback sweep (ex_geom)
+constexpr int CH_STAGEB = 5 * 64 * 16;
 constexpr int EX_MAXREJ = 4096;     // rejected fits per layer the fix-up handles
 constexpr int EX_DCAP = 8192;       // fix-up dirty-list capacity
 

@@ -261,7 +261,9 @@ __device__ bool ex_geom(const ExGeoArgs &A, int id, double *tb, const u64 *tab, 
     const int nd = __popcll(dl) + __popcll(dh);
     const long long bytes = ((8LL * (CH_HDR + 4 * nd + 6 * npad)) + 63) & ~63LL;
     unsigned long long off = 0;
-    if (nd > 64) {   // k_ex_chain forms one product per lane
+    // k_ex_chain forms one product per lane and stages CH_STAGEB bytes of a record (the tail
+    // of a longer one would keep what the wave's buffer held before)
+    if (nd > 64 || bytes > CH_STAGEB) {
         if (lane == 0) { ws.ctl[EXC_FALLBACK] = 1; ws.recoff[id] = -1; }
         return true;
     }

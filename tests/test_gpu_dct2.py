@@ -34,6 +34,10 @@ BIG = [(34, 38), (46, 34), (64, 34), (34, 64), (782, 646)]
 SLOTS = [(4, 2310), (2310, 4), (6, 8190), (8190, 6), (6, 1088), (1088, 6), (8, 5888), (4, 7168)]
 # the compile-time 8192 plan beside a generic one ((8192, 4): mode 1 on K2_8192)
 K8192 = [(4, 8192), (8192, 4), (4, 4096)]
+# odd n (Makhoul's reordering takes (n + 1) / 2 even samples): 3 = [3], 7 = [7], 9 = [9],
+# 15 = [3 5], 33 = [3 11], 51 = [3 17] (512 threads), 1155 = [3 5 7 11] (2 slots, the last
+# 131/1024), beside an even axis both ways round
+ODD = [(3, 3), (7, 8), (9, 9), (15, 22), (33, 33), (8, 51), (3, 1155), (1155, 4)]
 
 
 @pytest.fixture(scope="module")
@@ -81,7 +85,7 @@ def _case(mac, ny, nx):
 
 
 # ------------------------------------------------------------------ a. the solve --
-@pytest.mark.parametrize("shape", ONE_SLOT + BIG + SLOTS + K8192)
+@pytest.mark.parametrize("shape", ONE_SLOT + BIG + SLOTS + K8192 + ODD)
 def test_solve_against_long_double(env, shape):
     """rmt_mac_solve_poisson_neumann on a (ny, nx) context against idctn(dctn(rhs) / eig) in
     long double; the right-hand side keeps its mean, so the (0, 0) pin decides the result."""
@@ -124,7 +128,8 @@ def _host_pass(mode, x):
 
 # (context, axis, row counts): the rows of axis 0 are nx long, of axis 1 ny long.  (6, 46):
 # odd row counts, the last row without a partner in its workgroup
-ROW_CASES = [((6, 8190), 0, (6,)), ((1088, 6), 1, (6,)), ((6, 46), 0, (1, 3, 5))]
+ROW_CASES = [((6, 8190), 0, (6,)), ((1088, 6), 1, (6,)), ((6, 46), 0, (1, 3, 5)),
+             ((5, 45), 0, (2, 5)), ((1155, 4), 1, (3,))]
 
 
 @pytest.mark.parametrize("mode", [0, 2])
@@ -200,7 +205,7 @@ def test_row_pass_mean_on_load(env, shape):
 
 
 # ------------------------------------------------------------------ c. projection --
-@pytest.mark.parametrize("N", [30, 46, 90])
+@pytest.mark.parametrize("N", [30, 46, 90, 33])
 def test_projection_mixed_radix(env, N):
     """mac.project against the oracle at mixed-radix N (the mean on load, k_mac_rhs_rows and
     the solve; 46: the 512-thread variant), test_mac_projection's bars.  The wall-normal faces
@@ -248,10 +253,10 @@ def test_plan_reuse_after_custom_eigenvalues(env):
 
 
 # ------------------------------------------------------------------ e. rejection --
-@pytest.mark.parametrize("shape", [(7, 8), (8, 58), (8, 8194)])
+@pytest.mark.parametrize("shape", [(29, 8), (8, 58), (8, 8194)])
 def test_rejected_shapes(env, shape):
-    """Odd N, a prime factor > 23 (58 = 2 29) and N > 8192 raise NotImplementedError
-    (RMT_ENOTSUP).  dct2_plan tests the parity, factor() and lds_fits() of both axes before it
+    """A prime factor > 23 (29; 58 = 2 29) and N > 8192 raise NotImplementedError
+    (RMT_ENOTSUP).  dct2_plan tests factor() and lds_fits() of both axes before it
     allocates, uploads or launches anything, and rmt_mac_solve_poisson_neumann returns on its
     status, so no kernel runs: the output plane keeps its fill.  A process that met the
     refusal still solves a valid shape correctly."""
