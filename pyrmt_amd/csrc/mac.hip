@@ -15,8 +15,25 @@
 //   k_mac_diag      per-disc centroids over phi <= 0, max|u|
 // Every formula keeps the reference's NumPy operation order; only sin (H), the DCT and the
 // reductions' summation order differ from the reference in the last bits.
+//
+// The fused loop (rmt_mac_sim_step) is a resolved schedule and named phases, as sim.hip's:
+//   mac_sched           once per call, every decision that depends on the switches
+//                       (rmt_opts mac_*), the parameters and disc_phi(0, 0) but on no value a
+//                       step computes: box mode, the contact shortcut, face or centre sampling
+//                       of the SL advection, the source of its certificate's bound, the
+//                       stress grid (MacSched)
+//   mac_cover           per disc and step, host arithmetic on the map's support box
+//                       (mac_cover.hpp): the cells its passes cover, the rows and words the
+//                       no-op test scans; mac_diag_rows: the diagnostics' row range
+//   mac_start_boxes     the call's first full pass per disc (phi, support box)
+//   per step            mac_velocity_bound, mac_disc_update per disc, mac_stress_predict,
+//                       mac_project_impl, mac_diag (the step's one sync), mac_record (host)
+// Only hbox, t, diverged and diag (rmt_mac_sim) cross steps.  The slab step (rmt_mac_slab_*,
+// below) runs the same kernels on row ranges and shares mac_const, mac_params_check and
+// mac_upload_coords with the fused sim.
 #include "rmt_internal.hpp"
 #include "extrap.hpp"
+#include "mac_cover.hpp"
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -25,7 +42,7 @@
 namespace rmt {
 
 constexpr int MAC_MAXD = 8;
-// Box mode (rmt_mac_sim_step): disc k's map is zero and its phi = disc_phi(0, 0) > 0 outside
+// Box mode (mac_sched): disc k's map is zero and its phi = disc_phi(0, 0) > 0 outside
 // the cells b[k] = {j0, j1, i0, i1} (half-open); n = 0: no boxes (every cell may hold
 // anything).  contact: every disc_phi(0, 0) >= eps too, so a contact pair is +0.0 outside
 // either disc's box and the stress S is +0.0 outside the union of the boxes.
@@ -50,7 +67,7 @@ struct DiscSet {
 };
 
 // Index math of the per-cell / per-face kernels in 32 bits (a 64-bit division by a runtime
-// divisor is a long emulated sequence): every index fits, N <= 32768 (rmt_mac_sim_create).
+// divisor is a long emulated sequence): every index fits, N <= 32768 (mac_params_check).
 __device__ __forceinline__ int dv32(long x, int d) { return (int)((unsigned)x / (unsigned)d); }
 
 // Every kernel takes global row ranges and global-index plane pointers (pointer - lo * row
@@ -202,8 +219,9 @@ __global__ void __launch_bounds__(1024) k_box_reduce(const int2 *__restrict__ br
     }
     if (threadIdx.x < 4) box[threadIdx.x] = s[threadIdx.x][0];
 }
-// phi = disc_phi(X1, X2) over the grid and the support box (rmt_mac_sim_step's start in the
-// box mode: phi then holds disc_phi(0, 0) wherever the map is zero, as every later step keeps)
+// phi = disc_phi(X1, X2) over the grid and the support box (mac_start_boxes, a call's start in
+// the box mode: phi then holds disc_phi(0, 0) wherever the map is zero, as every later step
+// keeps)
 __global__ void __launch_bounds__(256) k_mac_box_phi(const double *__restrict__ X1,
                                                      const double *__restrict__ X2, int N,
                                                      double x0, double y0, double R,
@@ -373,6 +391,33 @@ __global__ void __launch_bounds__(MS_TPB) k_mac_stress(DiscSet D, int N, double 
 // k_mac_stress's zero-term skip needs 2 h >= 2^-30 and finite contact constants (see there)
 static bool stress_skip_ok(const rmt_mac_params &P) {
     return 2.0 * P.dx >= 0x1p-30 && std::isfinite(P.eta) && std::isfinite(2.0 * P.mu_s);
+}
+
+// The loop's derived constants (mac_multi_disc_lid.py:44-52), of the fused and the slab step
+struct MacConst {
+    double dx, dx2, w_t, eps, nu;
+};
+static MacConst mac_const(const rmt_mac_params &P) {
+    // dx2: the reference's dx**2 on a Python float (libm pow)
+    return {P.dx, std::pow(P.dx, 2.0), 2.0 * P.dx, 3.0 * P.dx, P.mu_f / P.rho};
+}
+// What rmt_mac_sim_create and rmt_mac_slab_create both require (grid_msg: the caller's words
+// for a context of another grid)
+static int mac_params_check(const rmt_ctx *ctx, const rmt_mac_params *prm, const char *grid_msg) {
+    RMT_CHECK(prm->n_discs >= 1 && prm->n_discs <= RMT_MAC_MAXD, RMT_EINVAL, "1..8 discs");
+    RMT_CHECK(prm->N >= 4 && prm->N <= 32768, RMT_EINVAL, "N in 4..32768 (32-bit face indices)");
+    RMT_CHECK(ctx->nx == prm->N && ctx->ny == prm->N, RMT_EINVAL, grid_msg);
+    return RMT_OK;
+}
+// index-grid coordinates (mac_multi_disc_lid.py:41): Xg = arange(N) * dx into xs and ys (ys
+// nullable) on the context's stream, which is drained (the staging vector ends here)
+static int mac_upload_coords(rmt_ctx *ctx, int N, double dx, double *xs, double *ys) {
+    std::vector<double> g(N);
+    for (int i = 0; i < N; ++i) g[i] = i * dx;
+    RMT_HIP(hipMemcpyAsync(xs, g.data(), N * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (ys) RMT_HIP(hipMemcpyAsync(ys, g.data(), N * 8, hipMemcpyHostToDevice, ctx->stream));
+    RMT_HIP(hipStreamSynchronize(ctx->stream));
+    return RMT_OK;
 }
 
 // utils.py grad_central at cell (j, i) of an N x N plane (one-sided at the edges)
@@ -719,12 +764,240 @@ struct rmt_mac_sim {
     double *mpartv;              // (the correction's max |v| partials: k_m2_bound)
     int *dbox;                   // [K][4] device support boxes (k_box_reduce), host copy:
     int hbox[RMT_MAC_MAXD][4];
+    // one step's read-backs (pageable), complete after the step's one sync (mac_diag)
+    std::vector<double> jr, dp;   // the stress blocks' (min J, max J); k_mac_diag's partials
+    double um;                    // max |u| of the correction's pass
+    int fl[4];                    // non-finite centre, non-finite sample, fitted, sweep aborted
     double t = 0;
     bool diverged = false;
     std::vector<rmt_mac_diag> diag;
 };
 
 using namespace rmt;
+
+// candidate capacity of the no-op test's list: 32 cells per grid row (a disc's rim holds
+// about 4 per row it spans; beyond the capacity k_ex_none_list walks the rows instead)
+static int mac_cand_cap(int N) { return 32 * N; }
+
+// The fused step's schedule, resolved once per call: every decision that depends on the
+// switches (rmt_opts mac_*) and the parameters but on no value the steps compute.
+struct MacSched : MacConst {   // (mac_sched explains each member where it sets it)
+    int N, K, G;
+    bool box_mode, face_sl, m2_bound, noop_host, stress_skip, stress_boxes;
+    int contact;
+    int sg[2];   // the stress grid; one (min J, max J) partial per block, npart() of them
+    int npart() const { return sg[0] * sg[1]; }
+    size_t kb_bytes;
+};
+
+static MacSched mac_sched(const rmt_mac_sim *S) {
+    const rmt_opts &o = S->ctx->opt;
+    const rmt_mac_params &P = S->P;
+    MacSched sc{};
+    static_cast<MacConst &>(sc) = mac_const(P);
+    sc.N = P.N; sc.K = P.n_discs;
+    // Box mode: a disc's advection, extrapolation and phi run only on its map's support box
+    // grown by G cells.  Exact when the origin lies outside every reference disc (disc_phi(0,
+    // 0) > 0): then a zero map cell is not known and its SL mask is 0, so the advected map is
+    // zero outside the old support, the extrapolation's targets lie within `layers` cells of
+    // known cells and it reads values within 4 more (9 x 9 windows), and phi = disc_phi(0, 0)
+    // wherever the map stays zero.  The box comes back with each step's diagnostics (no
+    // extra host round trip); a call starts with one full pass per disc (phi, box).
+    sc.G = P.layers + 6;
+    sc.box_mode = o.mac_boxes != 0 && P.layers > 0;
+    sc.contact = 1;
+    for (int k = 0; k < sc.K; ++k) {
+        const double p0 = std::sqrt(P.cx[k] * P.cx[k] + P.cy[k] * P.cy[k]) - P.R[k];
+        sc.box_mode = sc.box_mode && p0 > 0.0;
+        sc.contact = sc.contact && p0 >= sc.eps;   // (a contact term needs both phi < eps)
+    }
+    // the advection samples the faces itself (k_sim_sl_t<1>) or the cell-centre planes
+    sc.face_sl = o.mac_face_sl != 0;
+    // the SL certificate's bound (with face_sl): within a call the previous step's correction
+    // has the face maxima (k_m2_bound); off, or on a call's first step: the exact max pass
+    sc.m2_bound = o.mac_m2_bound != 0;
+    sc.noop_host = o.mac_noop_host != 0;   // the no-op verdict read back (ExtrapCall::none_host)
+    sc.stress_skip = stress_skip_ok(P);
+    // box mode with contact: the stress on the discs' boxes grown by 6 only (MS_BLOCKS / K
+    // blocks each); otherwise the whole grid
+    sc.stress_boxes = sc.box_mode && sc.contact;
+    sc.sg[0] = sc.stress_boxes ? MS_BLOCKS / sc.K : MS_BLOCKS;
+    sc.sg[1] = sc.stress_boxes ? sc.K : 1;
+    // the known plane, cleared ahead of each disc's advection in box mode
+    sc.kb_bytes = (size_t)sc.N * ((sc.N + 63) / 64) * sizeof(unsigned long long);
+    return sc;
+}
+
+// the discs' planes; bx.n: 0 when boxes are off, bx.b[k]: set per step (mac_disc_update)
+static DiscSet mac_discs(const rmt_mac_sim *S, const MacSched &sc) {
+    DiscSet D{};
+    D.K = sc.K;
+    for (int k = 0; k < sc.K; ++k) { D.X1[k] = S->X1[k]; D.X2[k] = S->X2[k]; D.phi[k] = S->phi[k]; }
+    D.bx.n = sc.box_mode ? sc.K : 0;
+    D.bx.contact = sc.contact;
+    return D;
+}
+
+// a call's start in box mode: one full pass per disc (phi, support box), the boxes read back
+static int mac_start_boxes(rmt_mac_sim *S, const MacSched &sc) {
+    const rmt_mac_params &P = S->P;
+    const int N = sc.N;
+    hipStream_t st = S->ctx->stream;
+    for (int k = 0; k < sc.K; ++k) {
+        k_mac_box_phi<<<dim3((N + 255) / 256, N), 256, 0, st>>>(
+            S->X1[k], S->X2[k], N, P.cx[k], P.cy[k], P.R[k], S->phi[k], S->bres);
+        k_box_reduce<<<1, 1024, 0, st>>>(S->bres, (N + 255) / 256, N, 0, S->dbox + 4 * k);
+        RMT_LAUNCHED();
+    }
+    RMT_HIP(hipMemcpyAsync(S->hbox, S->dbox, 4 * sc.K * sizeof(int), hipMemcpyDeviceToHost, st));
+    RMT_HIP(hipStreamSynchronize(st));
+    return RMT_OK;
+}
+
+// 1. the step's flags cleared, and max |u_c|^2 or a bound of it in out[8], which bounds every
+// velocity sample of the backtraces (the SL block skip).  it: the step's index in this call
+// (the caller may write u between calls)
+static int mac_velocity_bound(rmt_mac_sim *S, const MacSched &sc, int it) {
+    hipStream_t st = S->ctx->stream;
+    RMT_HIP(hipMemsetAsync(S->flags, 0, 5 * sizeof(int), st));   // [4]: k_mac_phi's big
+    // within a call the previous step's correction has the face maxima (m2_bound)
+    const bool m2b = sc.face_sl && it > 0 && sc.m2_bound;
+    if (m2b)
+        k_m2_bound<<<1, 1024, 0, st>>>(S->mpart, S->mpartv, MP_BLOCKS, S->flags, S->out + 8);
+    else if (sc.face_sl)
+        k_mac_centres_m2<false><<<MP_BLOCKS, RED_T, 0, st>>>(S->u, S->v, sc.N, S->uc, S->vc,
+                                                             S->flags, S->mpart);
+    else
+        k_mac_centres_m2<true><<<MP_BLOCKS, RED_T, 0, st>>>(S->u, S->v, sc.N, S->uc, S->vc,
+                                                            S->flags, S->mpart);
+    if (!m2b)
+        k_max_partials<false><<<1, 1024, 0, st>>>(S->mpart, MP_BLOCKS, -INFINITY, S->out + 8);
+    RMT_LAUNCHED();
+    return RMT_OK;
+}
+
+// 2. disc k: its covered cells into D.bx.b[k], SL-RK4 of the map with the pre-advection mask,
+// exact extrapolation, phi rebuilt (and, in box mode, the new map's support box)
+static int mac_disc_update(rmt_mac_sim *S, const MacSched &sc, DiscSet &D, int k, double dt) {
+    rmt_ctx *ctx = S->ctx;
+    const rmt_mac_params &P = S->P;
+    const int N = sc.N;
+    hipStream_t st = ctx->stream;
+    MacCover c{{0, N, 0, N}, {0, 0}, {0, 0}, false};   // boxes off: every cell, every row
+    if (sc.box_mode) {
+        c = mac_cover(S->hbox[k], N, sc.G);
+        RMT_HIP(hipMemsetAsync(S->kbits, 0, sc.kb_bytes, st));
+    }
+    for (int q = 0; q < 4; ++q) D.bx.b[k][q] = c.cb[q];   // (the stress / diag passes)
+    // phi from the current map (already S->phi[k]), advect with the pre-advection mask
+    RMT_TRY(sl_disc_map(ctx, S->X1[k], S->X2[k], sc.face_sl ? S->u : S->uc,
+                        sc.face_sl ? S->v : S->vc, S->xs, S->ys, dt, sc.dx, sc.dx, P.cx[k],
+                        P.cy[k], P.R[k], S->X1n, S->X2n, S->phi_pre, S->flags + 1, S->out + 8,
+                        S->kbits, sc.box_mode ? c.cb : nullptr, sc.face_sl));
+    // the known plane from the advection pass (its k_ex_bits pass over phi_pre saved); the
+    // no-op test over every row at once (a disc with nothing to fit scans them all), in box
+    // mode over the cover's rows and words
+    ExtrapCall ec;
+    ec.none_wide = true;
+    for (int q = 0; q < 2; ++q) {
+        ec.none_rows[q] = c.none_rows[q]; ec.none_cols[q] = c.none_cols[q];
+    }
+    ec.cand = S->cand; ec.cand_cap = mac_cand_cap(N);
+    ec.none_host = sc.noop_host;
+    RMT_TRY(extrapolate(ctx, S->X1n, S->X2n, S->phi_pre, sc.dx, sc.dx, P.layers, S->X1n, S->X2n,
+                        S->flags + 2, S->kbits, ec));
+    if (!sc.box_mode)
+        k_mac_phi<<<grid1d((long)N * N, 256), 256, 0, st>>>(S->X1n, S->X2n, (long)N * N, P.cx[k],
+                                                            P.cy[k], P.R[k], S->X1[k], S->X2[k],
+                                                            S->phi[k], S->flags + 4);
+    else if (!c.empty) {
+        const int *cb = c.cb;
+        const int nbx = (cb[3] - cb[2] + 255) / 256;
+        k_mac_phi_box<<<dim3(nbx, cb[1] - cb[0]), 256, 0, st>>>(
+            S->X1n, S->X2n, N, cb[0], cb[2], cb[3], P.cx[k], P.cy[k], P.R[k], S->X1[k], S->X2[k],
+            S->phi[k], S->flags + 4, S->bres);
+        k_box_reduce<<<1, 1024, 0, st>>>(S->bres, nbx, cb[1] - cb[0], cb[0], S->dbox + 4 * k);
+    } else {
+        k_box_reduce<<<1, 1024, 0, st>>>(S->bres, 0, 0, 0, S->dbox + 4 * k);   // empty
+    }
+    RMT_LAUNCHED();
+    return RMT_OK;
+}
+
+// 3. the stress (whole grid, or the boxes: MacSched::sg) with its J range partials on their
+// way to the host, then the predictor with the face force from S
+static int mac_stress_predict(rmt_mac_sim *S, const MacSched &sc, const DiscSet &D, double dt) {
+    const rmt_mac_params &P = S->P;
+    const int N = sc.N;
+    hipStream_t st = S->ctx->stream;
+    k_mac_stress<<<dim3(sc.sg[0], sc.sg[1]), MS_TPB, 0, st>>>(
+        D, N, sc.dx, sc.dx, P.mu_s, sc.w_t, P.eta, sc.eps, S->Sxx, S->Sxy, S->Syy, S->part, 0, N,
+        0, N, sc.stress_skip, S->flags + 4, sc.stress_boxes);
+    RMT_LAUNCHED();
+    RMT_HIP(hipMemcpyAsync(S->jr.data(), S->part, 2 * sc.npart() * sizeof(double),
+                           hipMemcpyDeviceToHost, st));
+    k_mac_predict<<<grid1d(2 * (long)N * (N + 1), 256), 256, 0, st>>>(
+        S->u, S->v, S->Sxx, S->Sxy, S->Syy, nullptr, nullptr, N, sc.nu, sc.dx, sc.dx, sc.dx2,
+        sc.dx2, dt, P.U_lid, P.rho, S->us, S->vs, FaceRows{0, N, 0, N + 1}, D.bx);
+    RMT_LAUNCHED();
+    return RMT_OK;
+}
+
+// 5. max |u| from the correction's pass, folded on the device into out[9]; the centroid
+// partials over the rows holding every box; the step's read-backs and its one sync (box
+// mode: the next step's boxes ride with the diagnostics)
+static int mac_diag(rmt_mac_sim *S, const MacSched &sc, const DiscSet &D) {
+    hipStream_t st = S->ctx->stream;
+    k_max_partials<true><<<1, 1024, 0, st>>>(S->mpart, MP_BLOCKS, 0.0, S->out + 9);
+    int dr[2];
+    mac_diag_rows(D.bx.b, D.bx.n, sc.N, dr);
+    k_mac_diag<<<MS_BLOCKS, MS_TPB, 0, st>>>(D, nullptr, sc.N, sc.dx, S->part + 2 * MS_BLOCKS, 0,
+                                             sc.N, dr[0], dr[1]);
+    RMT_LAUNCHED();
+    RMT_HIP(hipMemcpyAsync(S->dp.data(), S->part + 2 * MS_BLOCKS, S->dp.size() * 8,
+                           hipMemcpyDeviceToHost, st));
+    RMT_HIP(hipMemcpyAsync(&S->um, S->out + 9, sizeof(double), hipMemcpyDeviceToHost, st));
+    RMT_HIP(hipMemcpyAsync(S->fl, S->flags, sizeof(S->fl), hipMemcpyDeviceToHost, st));
+    if (sc.box_mode)
+        RMT_HIP(hipMemcpyAsync(S->hbox, S->dbox, 4 * sc.K * sizeof(int), hipMemcpyDeviceToHost, st));
+    RMT_HIP(hipStreamSynchronize(st));
+    return RMT_OK;
+}
+
+// 6. (host) the step's errors, which leave t and the records untouched; then t advanced and
+// the record folded from the read-backs
+static int mac_record(rmt_mac_sim *S, const MacSched &sc, double dt) {
+    RMT_CHECK(!S->fl[0] && !S->fl[1], RMT_ENONFINITE,
+              "advect_reference_map: non-finite velocity (the simulation diverged)");
+    RMT_CHECK(!S->fl[3], RMT_EDEVICE, extrap_abort_detail(S->fl[3]));
+    S->t += dt;
+    rmt_mac_diag r{};
+    r.t = S->t; r.dt = dt; r.n_discs = sc.K;
+    r.minJ = 1.0; r.maxJ = 1.0;
+    for (int b = 0; b < sc.npart(); ++b) {
+        r.minJ = std::fmin(r.minJ, S->jr[2 * b]); r.maxJ = std::fmax(r.maxJ, S->jr[2 * b + 1]);
+    }
+    double acc[MD_VALS] = {0};
+    for (int b = 0; b < MS_BLOCKS; ++b)
+        for (int k = 0; k < MD_VALS; ++k) {
+            const double x = S->dp[(size_t)b * MD_VALS + k];
+            acc[k] = k == 3 * MAC_MAXD ? nanmax(acc[k], x) : acc[k] + x;
+        }
+    for (int k = 0; k < sc.K; ++k) {
+        r.cx[k] = acc[3 * k + 2] > 0 ? acc[3 * k] / acc[3 * k + 2] : NAN;
+        r.cy[k] = acc[3 * k + 2] > 0 ? acc[3 * k + 1] / acc[3 * k + 2] : NAN;
+    }
+    acc[3 * MAC_MAXD] = nanmax(acc[3 * MAC_MAXD], S->um);
+    r.umax = acc[3 * MAC_MAXD];
+    // mac_multi_disc_lid.py:100-103: the driver stops on a non-finite u, a folded (J < 0)
+    // or over-stretched (J > 20) map, or a disc with no phi <= 0 cell left
+    bool lost = false;
+    for (int k = 0; k < sc.K; ++k) lost |= !(acc[3 * k + 2] > 0);
+    r.diverged = !std::isfinite(r.umax) || r.minJ < 0.0 || r.maxJ > 20.0 || lost;
+    S->diag.push_back(r);
+    S->diverged = r.diverged;   // (the loop stops ahead of the next step)
+    return RMT_OK;
+}
 
 extern "C" {
 
@@ -789,21 +1062,26 @@ int rmt_mac_momentum_predictor(rmt_ctx *ctx, const double *u, const double *v, d
 
 int rmt_mac_contact_stress(rmt_ctx *ctx, const double *phi_a, const double *phi_b, double eta,
                            double Gsum, double eps, double dx, double dy, double *txx,
-                           double *txy, double *tyy);
-
-// candidate capacity of the no-op test's list: 32 cells per grid row (a disc's rim holds
-// about 4 per row it spans; beyond the capacity k_ex_none_list walks the rows instead)
-static int mac_cand_cap(int N) { return 32 * N; }
+                           double *txy, double *tyy) {
+    RMT_CHECK(ctx && phi_a && phi_b && txx && txy && tyy && ctx->nx == ctx->ny, RMT_EINVAL,
+              "bad argument");
+    const int N = ctx->nx;
+    const long n = (long)N * N;
+    k_contact<<<grid1d(n, 256), 256, 0, ctx->stream>>>(phi_a, phi_b, N, eta, Gsum, eps, dx, dy,
+                                                       txx, txy, tyy);
+    RMT_LAUNCHED();
+    return RMT_OK;
+}
 
 int rmt_mac_sim_create(rmt_ctx *ctx, const rmt_mac_params *prm, rmt_mac_sim **out) {
     RMT_CHECK(ctx && prm && out, RMT_EINVAL, "null argument");
-    RMT_CHECK(prm->n_discs >= 1 && prm->n_discs <= RMT_MAC_MAXD, RMT_EINVAL, "1..8 discs");
-    RMT_CHECK(prm->N >= 4 && prm->N <= 32768, RMT_EINVAL, "N in 4..32768 (32-bit face indices)");
-    RMT_CHECK(ctx->nx == prm->N && ctx->ny == prm->N, RMT_EINVAL, "ctx grid != N x N");
+    RMT_TRY(mac_params_check(ctx, prm, "ctx grid != N x N"));
     const int N = prm->N;
     RMT_TRY(dct2_plan(ctx, N, N, prm->dx, prm->dx));
     rmt_mac_sim *S = new rmt_mac_sim;
     S->ctx = ctx; S->P = *prm;
+    S->jr.resize(2 * MS_BLOCKS);
+    S->dp.resize((size_t)MS_BLOCKS * MD_VALS);
     const long n = (long)N * N, nf = (long)N * (N + 1);
     const int K = prm->n_discs;
     const size_t dbl = 5 * nf + (9 + 3 * K) * n + 2 * N + (2 + MD_VALS) * MS_BLOCKS + 64 + 32 +
@@ -833,14 +1111,9 @@ int rmt_mac_sim_create(rmt_ctx *ctx, const rmt_mac_params *prm, rmt_mac_sim **ou
     S->mpartv = q; q += MP_BLOCKS;
     S->dbox = (int *)q; q += 4 * RMT_MAC_MAXD / 2;
     S->flags = (int *)q;
-    // index-grid coordinates (mac_multi_disc_lid.py:41): Xg = arange(N) * dx
-    std::vector<double> g(N);
-    for (int i = 0; i < N; ++i) g[i] = i * prm->dx;
-    RMT_HIP(hipMemcpyAsync(S->xs, g.data(), N * 8, hipMemcpyHostToDevice, ctx->stream));
-    RMT_HIP(hipMemcpyAsync(S->ys, g.data(), N * 8, hipMemcpyHostToDevice, ctx->stream));
     RMT_TRY(ensure_bytes(ctx, extrap_workspace(N, N, prm->layers)));
     RMT_HIP(hipMalloc(&S->cand, (mac_cand_cap(N) + 1) * sizeof(int)));
-    RMT_HIP(hipStreamSynchronize(ctx->stream));
+    RMT_TRY(mac_upload_coords(ctx, N, prm->dx, S->xs, S->ys));
     *out = S;
     return RMT_OK;
 }
@@ -867,189 +1140,23 @@ int rmt_mac_sim_field(rmt_mac_sim *S, int field, int disc, double **ptr) {
 
 int rmt_mac_sim_step(rmt_mac_sim *S, int nsteps, double t_end) {
     RMT_CHECK(S, RMT_EINVAL, "null sim");
-    rmt_ctx *ctx = S->ctx;
     const rmt_mac_params &P = S->P;
-    const int N = P.N, K = P.n_discs;
-    const long n = (long)N * N, nf = (long)N * (N + 1);
-    hipStream_t st = ctx->stream;
-    DiscSet D{};
-    D.K = K;
-    for (int k = 0; k < K; ++k) { D.X1[k] = S->X1[k]; D.X2[k] = S->X2[k]; D.phi[k] = S->phi[k]; }
-    const double dx = P.dx, w_t = 2.0 * dx, eps = 3.0 * dx, nu = P.mu_f / P.rho;
-    const double dx2 = std::pow(dx, 2.0);
-    // Box mode: a disc's advection, extrapolation and phi run only on its map's support box
-    // grown by G cells.  Exact when the origin lies outside every reference disc (disc_phi(0,
-    // 0) > 0): then a zero map cell is not known and its SL mask is 0, so the advected map is
-    // zero outside the old support, the extrapolation's targets lie within `layers` cells of
-    // known cells and it reads values within 4 more (9 x 9 windows), and phi = disc_phi(0, 0)
-    // wherever the map stays zero.  The box comes back with each step's diagnostics (no
-    // extra host round trip); a call starts with one full pass per disc (phi, box).
-    const int G = P.layers + 6;
-    bool box_mode = ctx->opt.mac_boxes != 0 && P.layers > 0;
-    D.bx.contact = 1;
-    for (int k = 0; k < K; ++k) {
-        const double p0 = std::sqrt(P.cx[k] * P.cx[k] + P.cy[k] * P.cy[k]) - P.R[k];
-        box_mode = box_mode && p0 > 0.0;
-        D.bx.contact = D.bx.contact && p0 >= eps;   // (a contact term needs both phi < eps)
-    }
-    D.bx.n = 0;   // set per step once the boxes are known
-    const size_t kb_bytes = (size_t)N * ((N + 63) / 64) * sizeof(unsigned long long);
-    if (box_mode && nsteps > 0 && S->t < t_end && !S->diverged) {
-        for (int k = 0; k < K; ++k) {
-            k_mac_box_phi<<<dim3((N + 255) / 256, N), 256, 0, st>>>(
-                S->X1[k], S->X2[k], N, P.cx[k], P.cy[k], P.R[k], S->phi[k], S->bres);
-            k_box_reduce<<<1, 1024, 0, st>>>(S->bres, (N + 255) / 256, N, 0, S->dbox + 4 * k);
-            RMT_LAUNCHED();
-        }
-        RMT_HIP(hipMemcpyAsync(S->hbox, S->dbox, 4 * K * sizeof(int), hipMemcpyDeviceToHost, st));
-        RMT_HIP(hipStreamSynchronize(st));
-    }
+    const MacSched sc = mac_sched(S);
+    DiscSet D = mac_discs(S, sc);
+    if (sc.box_mode && nsteps > 0 && S->t < t_end && !S->diverged)
+        RMT_TRY(mac_start_boxes(S, sc));
     for (int it = 0; it < nsteps; ++it) {
         if (!(S->t < t_end) || S->diverged) break;
         double dt = P.dt;
         if (S->t + dt > t_end) dt = t_end - S->t;
-        RMT_HIP(hipMemsetAsync(S->flags, 0, 5 * sizeof(int), st));   // [4]: k_mac_phi's big
-        // with max |u_c|^2, which bounds every velocity sample of the backtraces (the SL
-        // block skip)
-        const bool face_sl = ctx->opt.mac_face_sl != 0;
-        // within a call the previous step's correction has the face maxima (m2_bound)
-        const bool m2b = face_sl && it > 0 && ctx->opt.mac_m2_bound != 0;
-        if (m2b)
-            k_m2_bound<<<1, 1024, 0, st>>>(S->mpart, S->mpartv, MP_BLOCKS, S->flags, S->out + 8);
-        else if (face_sl)
-            k_mac_centres_m2<false><<<MP_BLOCKS, RED_T, 0, st>>>(S->u, S->v, N, S->uc, S->vc,
-                                                                 S->flags, S->mpart);
-        else
-            k_mac_centres_m2<true><<<MP_BLOCKS, RED_T, 0, st>>>(S->u, S->v, N, S->uc, S->vc,
-                                                                S->flags, S->mpart);
-        if (!m2b)
-            k_max_partials<false><<<1, 1024, 0, st>>>(S->mpart, MP_BLOCKS, -INFINITY, S->out + 8);
-        RMT_LAUNCHED();
-        for (int k = 0; k < K; ++k) {
-            int cb[4] = {0, N, 0, N};   // the cells this disc's passes cover
-            if (box_mode) {
-                D.bx.n = K;
-                const int *b = S->hbox[k];
-                if (b[1] < b[0]) { cb[1] = 0; cb[3] = 0; }   // empty map
-                else {
-                    cb[0] = std::max(0, b[0] - G); cb[1] = std::min(N, b[1] + 1 + G);
-                    cb[2] = std::max(0, b[2] - G); cb[3] = std::min(N, b[3] + 1 + G);
-                    // whole SL tiles: the phi pass covers exactly the cells they advected
-                    cb[0] -= cb[0] % 4; cb[1] = std::min(N, (cb[1] + 3) / 4 * 4);
-                    cb[2] -= cb[2] % 64; cb[3] = std::min(N, (cb[3] + 63) / 64 * 64);
-                }
-                RMT_HIP(hipMemsetAsync(S->kbits, 0, kb_bytes, st));
-            }
-            for (int q = 0; q < 4; ++q) D.bx.b[k][q] = cb[q];   // (the stress / diag passes)
-            // phi from the current map (already S->phi[k]), advect with the pre-advection mask
-            RMT_TRY(sl_disc_map(ctx, S->X1[k], S->X2[k], face_sl ? S->u : S->uc,
-                                face_sl ? S->v : S->vc, S->xs, S->ys, dt, dx, dx, P.cx[k],
-                                P.cy[k], P.R[k], S->X1n, S->X2n, S->phi_pre, S->flags + 1,
-                                S->out + 8, S->kbits, box_mode ? cb : nullptr, face_sl));
-            // the known plane from the advection pass (its k_ex_bits pass over phi_pre saved);
-            // the no-op test over every row at once (a disc with nothing to fit scans them all)
-            ExtrapCall ec;
-            ec.none_wide = true;
-            // box mode: the known cells lie in rows [cb0, cb1) (kbits cleared elsewhere), so a
-            // candidate -- an unknown 8-neighbour of a known cell -- in [cb0 - 1, cb1 + 1)
-            if (box_mode) {
-                ec.none_rows[0] = std::max(0, cb[0] - 1);
-                ec.none_rows[1] = cb[1] > cb[0] ? std::min(N, cb[1] + 1) : 1;
-                if (cb[1] <= cb[0]) ec.none_rows[0] = 0;   // (empty map: one row, no candidate)
-                // likewise the columns [cb2 - 1, cb3 + 1): their 64-column words
-                ec.none_cols[0] = std::max(0, cb[2] - 1) >> 6;
-                ec.none_cols[1] = cb[3] > cb[2] ? (std::min(N - 1, cb[3]) >> 6) + 1 : 1;
-            }
-            ec.cand = S->cand; ec.cand_cap = mac_cand_cap(N);
-            ec.none_host = ctx->opt.mac_noop_host != 0;
-            RMT_TRY(extrapolate(ctx, S->X1n, S->X2n, S->phi_pre, dx, dx, P.layers, S->X1n, S->X2n,
-                                S->flags + 2, S->kbits, ec));
-            if (!box_mode)
-                k_mac_phi<<<grid1d(n, 256), 256, 0, st>>>(S->X1n, S->X2n, n, P.cx[k], P.cy[k],
-                                                          P.R[k], S->X1[k], S->X2[k], S->phi[k],
-                                                          S->flags + 4);
-            else if (cb[1] > cb[0] && cb[3] > cb[2]) {
-                const int nbx = (cb[3] - cb[2] + 255) / 256;
-                k_mac_phi_box<<<dim3(nbx, cb[1] - cb[0]), 256, 0, st>>>(
-                    S->X1n, S->X2n, N, cb[0], cb[2], cb[3], P.cx[k], P.cy[k], P.R[k], S->X1[k],
-                    S->X2[k], S->phi[k], S->flags + 4, S->bres);
-                k_box_reduce<<<1, 1024, 0, st>>>(S->bres, nbx, cb[1] - cb[0], cb[0],
-                                                  S->dbox + 4 * k);
-            } else {
-                k_box_reduce<<<1, 1024, 0, st>>>(S->bres, 0, 0, 0, S->dbox + 4 * k);   // empty
-            }
-            RMT_LAUNCHED();
-        }
-        // box mode with contact: only the discs' boxes grown by 6 (MS_BLOCKS / K blocks each,
-        // one J partial per block); otherwise the whole grid
-        const bool sbox = D.bx.n > 0 && D.bx.contact;
-        const dim3 sg = sbox ? dim3(MS_BLOCKS / K, K) : dim3(MS_BLOCKS);
-        k_mac_stress<<<sg, MS_TPB, 0, st>>>(D, N, dx, dx, P.mu_s, w_t, P.eta, eps, S->Sxx,
-                                            S->Sxy, S->Syy, S->part, 0, N, 0, N,
-                                            stress_skip_ok(P), S->flags + 4, sbox);
-        RMT_LAUNCHED();
-        const int npart = (int)(sg.x * sg.y);
-        double jr[2 * MS_BLOCKS];
-        RMT_HIP(hipMemcpyAsync(jr, S->part, 2 * npart * sizeof(double), hipMemcpyDeviceToHost, st));
-        k_mac_predict<<<grid1d(2 * nf, 256), 256, 0, st>>>(S->u, S->v, S->Sxx, S->Sxy, S->Syy,
-                                                            nullptr, nullptr, N, nu, dx, dx, dx2,
-                                                            dx2, dt, P.U_lid, P.rho, S->us, S->vs,
-                                                            FaceRows{0, N, 0, N + 1}, D.bx);
-        RMT_LAUNCHED();
-        // max |u| from the correction's pass, folded on the device into out[9]
-        RMT_TRY(mac_project_impl(ctx, S->us, S->vs, dx, dx, dt, P.rho, S->u, S->v, S->p,
+        RMT_TRY(mac_velocity_bound(S, sc, it));
+        for (int k = 0; k < sc.K; ++k) RMT_TRY(mac_disc_update(S, sc, D, k, dt));
+        RMT_TRY(mac_stress_predict(S, sc, D, dt));
+        // 4. (the correction also leaves the face maxima: mac_diag, the next step's bound)
+        RMT_TRY(mac_project_impl(S->ctx, S->us, S->vs, sc.dx, sc.dx, dt, P.rho, S->u, S->v, S->p,
                                  S->X1n, true, S->mpart, S->mpartv));
-        k_max_partials<true><<<1, 1024, 0, st>>>(S->mpart, MP_BLOCKS, 0.0, S->out + 9);
-        int dr0 = 0, dr1 = N;   // the rows holding every box
-        if (D.bx.n) {
-            dr0 = N; dr1 = 0;
-            for (int k = 0; k < K; ++k)
-                if (D.bx.b[k][1] > D.bx.b[k][0]) {
-                    dr0 = std::min(dr0, D.bx.b[k][0]); dr1 = std::max(dr1, D.bx.b[k][1]);
-                }
-        }
-        k_mac_diag<<<MS_BLOCKS, MS_TPB, 0, st>>>(D, nullptr, N, dx, S->part + 2 * MS_BLOCKS, 0, N,
-                                                 dr0, dr1);
-        RMT_LAUNCHED();
-        std::vector<double> dp((size_t)MS_BLOCKS * MD_VALS);
-        RMT_HIP(hipMemcpyAsync(dp.data(), S->part + 2 * MS_BLOCKS, dp.size() * 8,
-                               hipMemcpyDeviceToHost, st));
-        double um = 0.0;
-        RMT_HIP(hipMemcpyAsync(&um, S->out + 9, sizeof(double), hipMemcpyDeviceToHost, st));
-        int fl[4];
-        RMT_HIP(hipMemcpyAsync(fl, S->flags, sizeof(fl), hipMemcpyDeviceToHost, st));
-        if (box_mode)   // the next step's boxes, with the diagnostics
-            RMT_HIP(hipMemcpyAsync(S->hbox, S->dbox, 4 * K * sizeof(int), hipMemcpyDeviceToHost, st));
-        RMT_HIP(hipStreamSynchronize(st));
-        RMT_CHECK(!fl[0] && !fl[1], RMT_ENONFINITE,
-                  "advect_reference_map: non-finite velocity (the simulation diverged)");
-        RMT_CHECK(!fl[3], RMT_EDEVICE, extrap_abort_detail(fl[3]));
-        S->t += dt;
-        rmt_mac_diag r{};
-        r.t = S->t; r.dt = dt; r.n_discs = K;
-        r.minJ = 1.0; r.maxJ = 1.0;
-        for (int b = 0; b < npart; ++b) {
-            r.minJ = std::fmin(r.minJ, jr[2 * b]); r.maxJ = std::fmax(r.maxJ, jr[2 * b + 1]);
-        }
-        double acc[MD_VALS] = {0};
-        for (int b = 0; b < MS_BLOCKS; ++b)
-            for (int k = 0; k < MD_VALS; ++k) {
-                const double x = dp[(size_t)b * MD_VALS + k];
-                acc[k] = k == 3 * MAC_MAXD ? nanmax(acc[k], x) : acc[k] + x;
-            }
-        for (int k = 0; k < K; ++k) {
-            r.cx[k] = acc[3 * k + 2] > 0 ? acc[3 * k] / acc[3 * k + 2] : NAN;
-            r.cy[k] = acc[3 * k + 2] > 0 ? acc[3 * k + 1] / acc[3 * k + 2] : NAN;
-        }
-        acc[3 * MAC_MAXD] = nanmax(acc[3 * MAC_MAXD], um);
-        r.umax = acc[3 * MAC_MAXD];
-        // mac_multi_disc_lid.py:100-103: the driver stops on a non-finite u, a folded (J < 0)
-        // or over-stretched (J > 20) map, or a disc with no phi <= 0 cell left
-        bool lost = false;
-        for (int k = 0; k < K; ++k) lost |= !(acc[3 * k + 2] > 0);
-        r.diverged = !std::isfinite(r.umax) || r.minJ < 0.0 || r.maxJ > 20.0 || lost;
-        S->diag.push_back(r);
-        if (r.diverged) { S->diverged = true; break; }
+        RMT_TRY(mac_diag(S, sc, D));
+        RMT_TRY(mac_record(S, sc, dt));
     }
     return RMT_OK;
 }
@@ -1059,19 +1166,6 @@ int rmt_mac_sim_diagnostics(rmt_mac_sim *S, rmt_mac_diag *out, int max_records, 
     const int m = (int)std::min<size_t>(S->diag.size(), (size_t)std::max(0, max_records));
     for (int k = 0; k < m; ++k) out[k] = S->diag[S->diag.size() - m + k];
     *n_records = (int)S->diag.size();
-    return RMT_OK;
-}
-
-int rmt_mac_contact_stress(rmt_ctx *ctx, const double *phi_a, const double *phi_b, double eta,
-                           double Gsum, double eps, double dx, double dy, double *txx,
-                           double *txy, double *tyy) {
-    RMT_CHECK(ctx && phi_a && phi_b && txx && txy && tyy && ctx->nx == ctx->ny, RMT_EINVAL,
-              "bad argument");
-    const int N = ctx->nx;
-    const long n = (long)N * N;
-    k_contact<<<grid1d(n, 256), 256, 0, ctx->stream>>>(phi_a, phi_b, N, eta, Gsum, eps, dx, dy,
-                                                       txx, txy, tyy);
-    RMT_LAUNCHED();
     return RMT_OK;
 }
 
@@ -1184,16 +1278,27 @@ struct rmt_mac_slab {
     }
 };
 
+// phi of disc k rebuilt from its new map (X1n, X2n -> X1, X2, phi) on rows r0-3 .. r1+3
+static int slab_phi(rmt_mac_slab *S, int k) {
+    const rmt_mac_params &P = S->P;
+    const int N = S->N;
+    const int jb = std::max(0, S->r0 - 3), je = std::min(N, S->r1 + 3);
+    const long o = (long)jb * N, n = (long)(je - jb) * N;
+    k_mac_phi<<<grid1d(n, 256), 256, 0, S->ctx->stream>>>(
+        S->gc(S->X1n[k]) + o, S->gc(S->X2n[k]) + o, n, P.cx[k], P.cy[k], P.R[k],
+        S->gc(S->X1[k]) + o, S->gc(S->X2[k]) + o, S->gc(S->phi[k]) + o);
+    RMT_LAUNCHED();
+    return RMT_OK;
+}
+
 extern "C" {
 
 int rmt_mac_slab_create(rmt_ctx *ctx, const rmt_mac_params *prm, int G, int rank,
                         const int *row_splits, const int *col_splits, rmt_mac_slab **out) {
     RMT_CHECK(ctx && prm && row_splits && col_splits && out, RMT_EINVAL, "null argument");
     RMT_CHECK(G >= 1 && G <= MSL_MAXG && rank >= 0 && rank < G, RMT_EINVAL, "slab: bad G/rank");
-    RMT_CHECK(prm->n_discs >= 1 && prm->n_discs <= RMT_MAC_MAXD, RMT_EINVAL, "1..8 discs");
-    RMT_CHECK(prm->N >= 4 && prm->N <= 32768, RMT_EINVAL, "N in 4..32768 (32-bit face indices)");
+    RMT_TRY(mac_params_check(ctx, prm, "slab: ctx must be the global N x N"));
     const int N = prm->N;
-    RMT_CHECK(ctx->nx == N && ctx->ny == N, RMT_EINVAL, "slab: ctx must be the global N x N");
     RMT_CHECK(N <= 8192, RMT_ENOTSUP, "MAC slab step: N <= 8192");
     for (int k = 0; k < G; ++k) {
         RMT_CHECK(row_splits[k + 1] - row_splits[k] >= RMT_SLAB_HALO + 1 && !(row_splits[k] & 1),
@@ -1247,11 +1352,8 @@ int rmt_mac_slab_create(rmt_ctx *ctx, const rmt_mac_params *prm, int G, int rank
     S->rowcnt = (int *)b;
     S->flags = S->rowcnt + rows + 32;
     S->nctl = S->flags + 32;
-    std::vector<double> g(N);
-    for (int i = 0; i < N; ++i) g[i] = i * prm->dx;   // mac_multi_disc_lid.py:41
-    RMT_HIP(hipMemcpyAsync(S->xs, g.data(), N * 8, hipMemcpyHostToDevice, ctx->stream));
     RMT_TRY(ensure_bytes(ctx, extrap_workspace(N, N, prm->layers)));
-    RMT_HIP(hipStreamSynchronize(ctx->stream));
+    RMT_TRY(mac_upload_coords(ctx, N, prm->dx, S->xs, nullptr));
     *out = S;
     return RMT_OK;
 }
@@ -1326,15 +1428,7 @@ int rmt_mac_slab_rim_pack(rmt_mac_slab *S) {
 // rim allgather and the dense replica
 int rmt_mac_slab_extrapolate_identity(rmt_mac_slab *S, int disc) {
     RMT_CHECK(S && disc >= 0 && disc < S->P.n_discs, RMT_EINVAL, "bad argument");
-    const rmt_mac_params &P = S->P;
-    const int N = S->N, k = disc;
-    const int jb = std::max(0, S->r0 - 3), je = std::min(N, S->r1 + 3);
-    const long o = (long)jb * N, n = (long)(je - jb) * N;
-    k_mac_phi<<<grid1d(n, 256), 256, 0, S->ctx->stream>>>(
-        S->gc(S->X1n[k]) + o, S->gc(S->X2n[k]) + o, n, P.cx[k], P.cy[k], P.R[k],
-        S->gc(S->X1[k]) + o, S->gc(S->X2[k]) + o, S->gc(S->phi[k]) + o);
-    RMT_LAUNCHED();
-    return RMT_OK;
+    return slab_phi(S, disc);
 }
 
 int rmt_mac_slab_extrapolate(rmt_mac_slab *S, int disc, const double *gathered,
@@ -1347,13 +1441,7 @@ int rmt_mac_slab_extrapolate(rmt_mac_slab *S, int disc, const double *gathered,
     RMT_TRY(slab_rim_extrapolate(ctx, gathered, counts, S->G, cap, S->X1d, S->X2d, S->bits[k],
                                  P.dx, P.dx, P.layers, S->flags + 4 + 2 * k, S->gc(S->X1n[k]),
                                  S->gc(S->X2n[k]), (long)S->lo * N, (long)S->hi * N));
-    const int jb = std::max(0, S->r0 - 3), je = std::min(N, S->r1 + 3);
-    const long o = (long)jb * N, n = (long)(je - jb) * N;
-    k_mac_phi<<<grid1d(n, 256), 256, 0, ctx->stream>>>(
-        S->gc(S->X1n[k]) + o, S->gc(S->X2n[k]) + o, n, P.cx[k], P.cy[k], P.R[k],
-        S->gc(S->X1[k]) + o, S->gc(S->X2[k]) + o, S->gc(S->phi[k]) + o);
-    RMT_LAUNCHED();
-    return RMT_OK;
+    return slab_phi(S, k);
 }
 
 int rmt_mac_slab_predict(rmt_mac_slab *S, double dt) {
@@ -1361,18 +1449,18 @@ int rmt_mac_slab_predict(rmt_mac_slab *S, double dt) {
     rmt_ctx *ctx = S->ctx;
     const rmt_mac_params &P = S->P;
     const int N = S->N, rows = S->r1 - S->r0;
-    const double dx = P.dx, w_t = 2.0 * dx, eps = 3.0 * dx, nu = P.mu_f / P.rho;
-    const double dx2 = std::pow(dx, 2.0);
+    const MacConst c = mac_const(P);
+    const double dx = c.dx;
     const DiscSet D = S->discs();
     k_mac_stress<<<MS_BLOCKS, MS_TPB, 0, ctx->stream>>>(
-        D, N, dx, dx, P.mu_s, w_t, P.eta, eps, S->gc(S->Sxx), S->gc(S->Sxy), S->gc(S->Syy),
+        D, N, dx, dx, P.mu_s, c.w_t, P.eta, c.eps, S->gc(S->Sxx), S->gc(S->Sxy), S->gc(S->Syy),
         S->part, std::max(0, S->r0 - 2), std::min(N, S->r1 + 2), S->r0, S->r1,
         stress_skip_ok(P));
     RMT_LAUNCHED();
     const FaceRows F{S->r0, S->r1, S->r0, std::min(S->r1 + 1, N + 1)};
     k_mac_predict<<<grid1d(face_count(F, N), 256), 256, 0, ctx->stream>>>(
         S->gu(S->u), S->gc(S->v), S->gc(S->Sxx), S->gc(S->Sxy), S->gc(S->Syy), nullptr, nullptr,
-        N, nu, dx, dx, dx2, dx2, dt, P.U_lid, P.rho, S->gu(S->us), S->gc(S->vs), F);
+        N, c.nu, dx, dx, c.dx2, c.dx2, dt, P.U_lid, P.rho, S->gu(S->us), S->gc(S->vs), F);
     RMT_LAUNCHED();
     double *rhs_g = S->rhs - (long)S->r0 * N;
     k_mac_rhs<<<grid1d((long)rows * N, 256), 256, 0, ctx->stream>>>(

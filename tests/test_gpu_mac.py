@@ -139,6 +139,20 @@ def test_mac_sim_stops_on_divergence(M):
     assert len(sim.diagnostics()["t"]) == 1
 
 
+def test_mac_sim_raises_on_non_finite_velocity(M):
+    """A NaN in u is an error return of the step that meets it (RMT_ENONFINITE, which the
+    binding raises as FloatingPointError): the step leaves no record, and the next call, on
+    the fields that step left, fails the same way."""
+    sim = M.MacMultiDisc(16, specs=[(0.2, 0.5, 0.5)])
+    sim.field("u")[8, 8] = float("nan")
+    with pytest.raises(FloatingPointError, match="advect_reference_map: non-finite velocity"):
+        sim.step(2)
+    assert len(sim.diagnostics()["t"]) == 0
+    with pytest.raises(FloatingPointError, match="advect_reference_map: non-finite velocity"):
+        sim.step(1)
+    assert len(sim.diagnostics()["t"]) == 0
+
+
 def test_mac_sim_raises_on_extrapolation_abort(M, gpu):
     """An aborted extrapolation is an error (RMTError), not a silently unfinished band."""
     from pyrmt_amd import _lib as L

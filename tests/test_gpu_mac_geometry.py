@@ -1,5 +1,5 @@
-"""The config-5 MAC loop (rmt_mac_sim_step) where its geometry-dependent decisions change:
-the cases of tests/test_mac_geometry_cpu.py (discs at and across walls, K = 1, 5, 8, N no
+"""The config-5 MAC loop (rmt_mac_sim_step) where its geometry-dependent decisions (mac_sched
+per call; mac_cover, mac_diag_rows and the stress grid per step) change: the cases of tests/test_mac_geometry_cpu.py (discs at and across walls, K = 1, 5, 8, N no
 multiple of 4 or 64 and odd, a box wider than 256 columns, the origin near and inside a disc,
 a grid smaller than one SL tile) against the oracle, and every implementation switch against
 the full-grid passes bit for bit.  Then the t_end clipping of the last step, the empty map, and

@@ -1,9 +1,10 @@
 """Geometry cases of the config-5 MAC loop (rmt_mac_sim_step) and the conditions that make a
 device-against-oracle comparison on them meaningful.  No GPU: the oracle alone.
 
-rmt_mac_sim_step decides per disc where it works (support boxes grown, clamped and rounded to
-SL tiles; the stress launched on the boxes; the predictor's zero force away from them; the
-diagnostics' row range; box mode and the contact shortcut switched by disc_phi(0, 0)).  The
+The loop decides per disc where it works: mac_cover grows, clamps and rounds the support
+boxes to SL tiles (mac_disc_update); mac_stress_predict launches the stress on the boxes and
+the predictor adds a zero force away from them; mac_diag_rows gives the diagnostics' row
+range; mac_sched switches box mode and the contact shortcut by disc_phi(0, 0).  The
 cases below put discs where those decisions change: at and across walls, K = 1, 5 and 8, N not
 a multiple of 4 or 64, a box wider than one 256-column block, the origin near and inside a
 disc.  tests/test_gpu_mac_geometry.py runs the device loop on the same table.
@@ -76,8 +77,9 @@ def initial_flow(name):
 
 
 def covered(box, N, G):
-    """The cells rmt_mac_sim_step's passes cover for a support box: grown by G, clamped,
-    rounded out to whole 4 x 64 SL tiles ((j0, j1, i0, i1), half-open)."""
+    """The cells mac_disc_update's passes cover for a support box (mac_cover's cb, held to
+    it by test_covered_restates_mac_cover): grown by G, clamped, rounded out to whole 4 x 64
+    SL tiles ((j0, j1, i0, i1), half-open)."""
     cb = [max(0, box[0] - G), min(N, box[1] + 1 + G), max(0, box[2] - G), min(N, box[3] + 1 + G)]
     cb[0] -= cb[0] % 4; cb[1] = min(N, (cb[1] + 3) // 4 * 4)
     cb[2] -= cb[2] % 64; cb[3] = min(N, (cb[3] + 63) // 64 * 64)
@@ -93,7 +95,7 @@ EMPTY = (32, [(0.004, 0.5, 0.5), (0.12, 0.3, 0.6)])
 
 
 def origin_phi(spec):
-    """disc_phi(0, 0): what rmt_mac_sim_step switches box mode and the contact shortcut on."""
+    """disc_phi(0, 0): what mac_sched switches box mode and the contact shortcut on."""
     R, cx, cy = spec
     return np.sqrt(cx * cx + cy * cy) - R
 
@@ -173,6 +175,64 @@ def test_swirl_supports_leave_their_tiles():
             grow = max(grow, o[0] - n[0], n[1] - o[1], o[2] - n[2], n[3] - o[3])
     assert left >= 1 and grow == 1, (left, grow)
     assert 0.7 < max(np.abs(a).max() for a in initial_flow("swirl")) <= 0.75
+
+
+LAYERS = 3      # the loop's extrapolation layers (mac_params; the oracle's MacMultiDisc)
+
+
+def cover_edge_inputs():
+    """(N, G, box) beyond the cases' boxes: an empty box (k_box_reduce's), a box touching all
+    four walls, and per N boxes whose grown upper column i1 + 1 + G lands exactly on a
+    multiple of 64, on N and on N - 1 (where a grid of that size has such a column)."""
+    out = [(32, 9, (2 ** 31 - 1, -1, 2 ** 31 - 1, -1)), (50, 9, (0, 49, 0, 49))]
+    for N in (9, 33, 50, 64, 320):
+        out += [(N, 9, (2 ** 31 - 1, -1, 2 ** 31 - 1, -1)), (N, 9, (0, N - 1, 0, N - 1))]
+        for G in (3, 9):
+            for top in sorted({64, 128, 256, N - 1, N}):
+                i1 = top - 1 - G
+                if 0 <= i1 < N:
+                    i0 = max(0, i1 - 5)
+                    out += [(N, G, (i0, i1, i0, i1)), (N, G, (1, min(N - 1, 3), 0, i1))]
+    return out
+
+
+def test_covered_restates_mac_cover(tmp_path):
+    """covered() above against mac_cover of pyrmt_amd/csrc/mac_cover.hpp (compiled for the
+    host: tools/mac_cover_check.hip), on every support box of every case and the edge inputs;
+    the no-op test's rows and words against their definition: rows [cb0 - 1, cb1 + 1) within
+    the grid, the 64-column words of columns [cb2 - 1, cb3 + 1) within it, and one row, one
+    word and no cell for an empty box."""
+    import os
+    import subprocess
+    from conftest import ROOT
+    inputs = cover_edge_inputs()
+    for name in sorted(CASES):
+        r = oracle_run(name)
+        for boxes in [r["box0"]] + r["boxes"]:
+            inputs += [(CASES[name][0], LAYERS + 6, b) for b in boxes]
+    exe = str(tmp_path / "mac_cover_check")
+    subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-o", exe,
+                    os.path.join(ROOT, "tools", "mac_cover_check.hip")], check=True)
+    text = "".join("%d %d %d %d %d %d\n" % ((N, G) + tuple(b)) for N, G, b in inputs)
+    r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=60, check=True)
+    rows = [[int(x) for x in line.split()] for line in r.stdout.splitlines()]
+    assert len(rows) == len(inputs) >= 100
+    tops = set()
+    for (N, G, b), got in zip(inputs, rows):
+        cb, none_rows, none_cols, empty = got[:4], got[4:6], got[6:8], got[8]
+        assert empty == (b[1] < b[0]), (N, G, b)
+        if empty:
+            assert (cb, none_rows, none_cols) == ([0, 0, 0, 0], [0, 1], [0, 1]), (N, G, b)
+            continue
+        assert cb == covered(b, N, G), (N, G, b, cb)
+        assert none_rows == [max(0, cb[0] - 1), min(N, cb[1] + 1)], (N, G, b, none_rows)
+        cols = [i for i in range(cb[2] - 1, cb[3] + 1) if 0 <= i < N]
+        assert none_cols == [cols[0] // 64, cols[-1] // 64 + 1], (N, G, b, none_cols)
+        tops.add((N, b[3] + 1 + G))
+    # the edge inputs reach what they are for
+    for N in (9, 33, 50, 64, 320):
+        assert {(N, N - 1), (N, N)} <= tops
+    assert {(320, 64), (320, 128), (320, 256), (64, 64)} <= tops
 
 
 def test_cut_support_has_column_0():
