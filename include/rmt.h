@@ -588,6 +588,42 @@ int rmt_mac_per_steps(rmt_ctx *ctx, double *u, double *v, double nu, double dx, 
                       double rho_dt, double dt_rho, const double *lx, const double *ly, int imex,
                       int nsteps, double *p);
 
+/* ---- periodic MAC tier, semi-Lagrangian predictor (macper_sl.hip): mac.py:587-633 ----
+ * Cubic B-spline interpolation on a periodic plane, scipy.ndimage's order 3, mode
+ * "grid-wrap": the prefilter wraps and pads nothing, every tap wraps by an integer modulo.
+ * Equal to rounding against scipy (the prefilter runs as windowed two-sided sums, 48 terms
+ * a side, parallel within a line), never bit for bit.  Workspace from the context. */
+/* the coefficient plane of f, axis 0 then axis 1 (what map_coordinates' prefilter=True makes
+ * inside mac.py:597-598); out may be f */
+int rmt_mac_per_spline_prefilter(rmt_ctx *ctx, const double *f, double *out);
+/* _interp_per(f, iq, jq) at nq points, f[j, i] at index (i, j): iq, jq, out device arrays of
+ * nq doubles, any finite coordinate */
+int rmt_mac_per_interp(rmt_ctx *ctx, const double *f, const double *iq, const double *jq,
+                       int nq, double *out);                              /* mac.py:593-598 */
+/* _sl_advect_per: f at offset (ox, oy) advected by the face velocities uf (offset (0, 1/2))
+ * and vf ((1/2, 0)), RK2 midpoint backtrace, five interpolations a point; out may be f */
+int rmt_mac_per_sl_advect(rmt_ctx *ctx, const double *f, const double *uf, const double *vf,
+                          double ox, double oy, double dx, double dy, double dt,
+                          double *out);                                   /* mac.py:601-614 */
+/* cfl = dt * max(max|u| / dx, max|v| / dy) is formed on the device (Python's max, NaN as
+ * np.max); cfl <= cfl_switch: rmt_mac_per_predictor_imex, the same bits; else u, v advected by
+ * themselves and two Helmholtz solves.  took_sl (may be NULL): 1 for the SL branch.
+ * u_star, v_star distinct from u, v and from each other. */
+int rmt_mac_per_predictor_semilag(rmt_ctx *ctx, const double *u, const double *v, double twodx,
+                                  double twody, double dx, double dy, double dt, double coef,
+                                  double cfl_switch, const double *lx, const double *ly,
+                                  double *u_star, double *v_star,
+                                  int *took_sl);                          /* mac.py:617-633 */
+/* rmt_mac_per_steps with that predictor (integrator "imex-sl" of
+ * benchmarks/mac_taylor_green_convergence.py:47-66): the branch of every step is decided and
+ * taken on the device, no host read inside the loop.  sl_steps (may be NULL): the number of
+ * the nsteps steps that took the SL branch, read once after the last one. */
+int rmt_mac_per_steps_sl(rmt_ctx *ctx, double *u, double *v, double nu, double dx, double dy,
+                         double dx2, double dy2, double twodx, double twody, double dt,
+                         double coef, double rho_dt, double dt_rho, const double *lx,
+                         const double *ly, double cfl_switch, int nsteps, double *p,
+                         int *sl_steps);
+
 /* The MAC step decomposed into row slabs (config 5 on several GPUs).
  * No reference interface: pyRMT runs mac_multi_disc_lid.py:62-98 in one process.  Slab
  * `rank` of G owns cell rows [row_splits[rank], row_splits[rank+1]) (even, > RMT_SLAB_HALO

@@ -210,6 +210,14 @@ SIGNATURES = {
     "rmt_mac_per_project": (_I, [_P, _P, _P, _D, _D, _D, _D, _P, _P, _P, _P, _P]),
     "rmt_mac_per_steps": (_I, [_P, _P, _P, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _P, _P,
                                _I, _I, _P]),
+    # ... its semi-Lagrangian predictor (macper_sl.hip)
+    "rmt_mac_per_spline_prefilter": (_I, [_P, _P, _P]),
+    "rmt_mac_per_interp": (_I, [_P, _P, _P, _P, _I, _P]),
+    "rmt_mac_per_sl_advect": (_I, [_P, _P, _P, _P, _D, _D, _D, _D, _D, _P]),
+    "rmt_mac_per_predictor_semilag": (_I, [_P, _P, _P, _D, _D, _D, _D, _D, _D, _D, _P, _P, _P,
+                                           _P, ctypes.POINTER(_I)]),
+    "rmt_mac_per_steps_sl": (_I, [_P, _P, _P, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _P, _P,
+                                  _D, _I, _P, ctypes.POINTER(_I)]),
 }
 
 _lib = None

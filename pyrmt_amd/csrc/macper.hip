@@ -7,6 +7,7 @@
 // ny x (nx/2+1) half-spectrum and Z2D (the reference: numpy.fft.fft2 / ifft2, pocketfft), equal
 // to rounding.  The loop's explicit step is two stencil kernels around the FFT pair:
 // k_macp_predict_div (option macp_fused) and k_macp_correct.
+#include "macper.hpp"
 #include "rocfft_util.hpp"
 
 namespace rmt {
@@ -24,7 +25,7 @@ void macper_destroy(MacPerPlan *P) {
 }
 
 // The context's plan for its (ny, nx) (made once), with the call's symbol uploaded.
-static int macp_plan(rmt_ctx *ctx, const double *lx, const double *ly) {
+int macp_plan(rmt_ctx *ctx, const double *lx, const double *ly) {
     const int ny = ctx->ny, nx = ctx->nx;
     RMT_CHECK(ny >= 2 && nx >= 2, RMT_EINVAL, "periodic MAC solve: ny, nx >= 2");
     MacPerPlan *P = ctx->macper;
@@ -52,48 +53,10 @@ static int macp_plan(rmt_ctx *ctx, const double *lx, const double *ly) {
     return RMT_OK;
 }
 
-// Workspace of the context, in doubles: the half-spectrum first (16-byte aligned), then
-// `planes` real planes of ny * nx rounded up to an even count.
-static inline size_t macp_spec(const rmt_ctx *ctx) {
-    return 2 * (size_t)ctx->ny * (ctx->nx / 2 + 1);
-}
-static inline size_t macp_plane(const rmt_ctx *ctx) {
-    return ((size_t)ctx->ny * ctx->nx + 1) & ~(size_t)1;
-}
-static int macp_workspace(rmt_ctx *ctx, int planes) {
-    return ensure_scratch(ctx, (macp_spec(ctx) + planes * macp_plane(ctx)) * sizeof(double));
-}
-
-struct MacpCoef { double nu, dx2, dy2, twodx, twody, dt; };
-
-// mac.py:639-644 (imex 0: u + dt * ru) and :530-532, 538 (imex 1: u - dt * adv_u) at one
-// u-face; v00 .. vNW: _v_at_u_per's four terms in its order (v, west, north, north-west)
-__device__ __forceinline__ double macp_ustar(double uc, double uE, double uW, double uN,
-                                             double uS, double v00, double vW, double vN,
-                                             double vNW, const MacpCoef &k, int imex) {
-    const double dudx = (uE - uW) / k.twodx;
-    const double dudy = (uN - uS) / k.twody;
-    const double vau = 0.25 * (((v00 + vW) + vN) + vNW);
-    const double adv = uc * dudx + vau * dudy;
-    if (imex) return uc - k.dt * adv;
-    const double lap = ((uE - 2.0 * uc) + uW) / k.dx2 + ((uN - 2.0 * uc) + uS) / k.dy2;
-    const double ru = -adv + k.nu * lap;
-    return uc + k.dt * ru;
-}
-
-// mac.py:645-650 / :534-536, 539 at one v-face; u00 .. uSE: _u_at_v_per's four terms in its
-// order (u, east, south, south-east)
-__device__ __forceinline__ double macp_vstar(double vc, double vE, double vW, double vN,
-                                             double vS, double u00, double uE, double uS,
-                                             double uSE, const MacpCoef &k, int imex) {
-    const double dvdx = (vE - vW) / k.twodx;
-    const double dvdy = (vN - vS) / k.twody;
-    const double uav = 0.25 * (((u00 + uE) + uS) + uSE);
-    const double adv = uav * dvdx + vc * dvdy;
-    if (imex) return vc - k.dt * adv;
-    const double lap = ((vE - 2.0 * vc) + vW) / k.dx2 + ((vN - 2.0 * vc) + vS) / k.dy2;
-    const double rv = -adv + k.nu * lap;
-    return vc + k.dt * rv;
+// the workspace laid out in macper.hpp
+int macp_workspace(rmt_ctx *ctx, int planes, size_t tail) {
+    return ensure_scratch(ctx,
+                          (macp_spec(ctx) + planes * macp_plane(ctx) + tail) * sizeof(double));
 }
 
 // mac.py:449-450, times s (project_per's rho / dt; 1.0 is exact)
@@ -142,11 +105,6 @@ __global__ void k_macp_predict(const double *__restrict__ u, const double *__res
 // s * div(u*, v*) are written.
 constexpr int MACP_TX = 64, MACP_TY = 16, MACP_WX = MACP_TX + 3, MACP_WY = MACP_TY + 3;
 constexpr int MACP_THREADS = 256;
-
-__device__ __forceinline__ int macp_wrap(int i, int n) {
-    i %= n;
-    return i < 0 ? i + n : i;
-}
 
 __global__ __launch_bounds__(MACP_THREADS) void k_macp_predict_div(
     const double *__restrict__ u, const double *__restrict__ v, int ny, int nx, MacpCoef k,
@@ -216,7 +174,7 @@ __global__ void k_macp_correct(const double *__restrict__ phi, const double *__r
 }
 
 // in -> out (may be the same plane) through the context's half-spectrum workspace
-static int macp_solve(rmt_ctx *ctx, const double *in, int mode, double coef, double *out) {
+int macp_solve(rmt_ctx *ctx, const double *in, int mode, double coef, double *out) {
     MacPerPlan *P = ctx->macper;
     const int ny = P->ny, nx = P->nx, h = nx / 2 + 1;
     hipStream_t st = ctx->stream;
@@ -252,8 +210,8 @@ static int macp_imex_predict(rmt_ctx *ctx, const double *u, const double *v, con
 }
 
 // mac.py:476-480 from the scaled divergence in phi: solve in place, correct
-static int macp_project_rhs(rmt_ctx *ctx, const double *us, const double *vs, double dx,
-                            double dy, double dt_rho, double *u, double *v, double *phi) {
+int macp_project_rhs(rmt_ctx *ctx, const double *us, const double *vs, double dx, double dy,
+                     double dt_rho, double *u, double *v, double *phi) {
     const long n = (long)ctx->ny * ctx->nx;
     RMT_TRY(macp_solve(ctx, phi, 0, 0.0, phi));
     k_macp_correct<<<grid1d(n, 256), 256, 0, ctx->stream>>>(phi, us, vs, ctx->ny, ctx->nx, dx, dy,
@@ -262,8 +220,8 @@ static int macp_project_rhs(rmt_ctx *ctx, const double *us, const double *vs, do
     return RMT_OK;
 }
 
-static int macp_div(rmt_ctx *ctx, const double *u, const double *v, double dx, double dy,
-                    double s, double *out) {
+int macp_div(rmt_ctx *ctx, const double *u, const double *v, double dx, double dy, double s,
+             double *out) {
     const long n = (long)ctx->ny * ctx->nx;
     k_macp_div<<<grid1d(n, 256), 256, 0, ctx->stream>>>(u, v, ctx->ny, ctx->nx, dx, dy, s, out);
     RMT_LAUNCHED();

@@ -6,8 +6,9 @@ Layout as the reference: p / phi (Ny, Nx) cell centres, u (Ny, Nx+1) x-faces,
 v (Ny+1, Nx) y-faces (square grids: Nx == Ny, checked by _lid_n; solve_poisson_neumann alone
 takes Ny != Nx).  ``MacMultiDisc`` is the device-resident loop body of
 benchmarks/mac_multi_disc_lid.py:36-98 (K soft discs with pair contact).
-The periodic tier (mac.py:445-540, 636-650; rmt_mac_per_*) keeps u, v and p all (Ny, Nx);
-``MacTaylorGreen`` / ``taylor_green_run_one`` are benchmarks/mac_taylor_green_convergence.py.
+The periodic tier (mac.py:445-540, 587-650; rmt_mac_per_*) keeps u, v and p all (Ny, Nx);
+``MacTaylorGreen`` / ``taylor_green_run_one`` are benchmarks/mac_taylor_green_convergence.py,
+its semi-Lagrangian integrator behind ``semilag=True``.
 """
 import ctypes
 import math
@@ -285,14 +286,28 @@ def contact_stress(phi_a, phi_b, eta, Gsum, eps, dx, dy):
 
 
 # ------------------------------------------------------------------ periodic tier ----
-# mac.py:445-540, 636-650 through macper.hip: u (x-faces), v (y-faces) and p (centres) are all
-# (Ny, Nx) planes and every index wraps.  The stencil operators are bit-exact; the solves go
-# through rocFFT on the half-spectrum (the reference: numpy.fft), equal to rounding.  Not
-# covered: momentum_predictor_periodic_semilag / _interp_per (grid-wrap cubic splines),
+# mac.py:445-540, 587-650 through macper.hip and macper_sl.hip: u (x-faces), v (y-faces) and p
+# (centres) are all (Ny, Nx) planes and every index wraps.  The stencil operators are
+# bit-exact; the solves go through rocFFT on the half-spectrum (the reference: numpy.fft) and
+# the grid-wrap cubic splines of the semi-Lagrangian predictor through a windowed prefilter
+# (the reference: scipy.ndimage), both equal to rounding.  Not covered:
 # momentum_predictor_periodic_imex_elastic, momentum_predictor_freeslip,
 # advect_xi_conservative, interfacial_force_faces.
-def _pctx(shape):
-    return ctx_for(shape[0], shape[1]).bind()
+_small_ctxs = {}
+
+
+def _pctx(shape, small=False):
+    """small: the spline operators and the two predictors they switch between take extents
+    from 2; below the stencil contexts' 5 they get a context of their own (no collocated
+    stencil is ever called on it)."""
+    ny, nx = int(shape[0]), int(shape[1])
+    if small and min(ny, nx) < 5:
+        from .functions import _Ctx, _torch
+        key = (ny, nx, _torch().cuda.current_device())
+        if key not in _small_ctxs:
+            _small_ctxs[key] = _Ctx(ny, nx, key[2], stencils=False)
+        return _small_ctxs[key].bind()
+    return ctx_for(ny, nx).bind()
 
 
 def _hp(a):
@@ -424,11 +439,85 @@ def momentum_predictor_periodic_imex(u, v, nu, dx, dy, dt, lap_eig):
     if tuple(ud.shape) != (ly.size, lx.size):
         raise ValueError("momentum_predictor_periodic_imex: the fields and lap_eig differ in shape")
     us = io.empty(ud.shape); vs = io.empty(ud.shape)
-    L.check(L.lib().rmt_mac_per_predictor_imex(_pctx(ud.shape), _p(ud), _p(vd), float(2 * dx),
-                                               float(2 * dy), float(dt), float(dt * nu),
-                                               _hp(lx), _hp(ly), _p(us), _p(vs)),
+    L.check(L.lib().rmt_mac_per_predictor_imex(_pctx(ud.shape, True), _p(ud), _p(vd),
+                                               float(2 * dx), float(2 * dy), float(dt),
+                                               float(dt * nu), _hp(lx), _hp(ly), _p(us), _p(vs)),
             "momentum_predictor_periodic_imex")
     return io.out(us), io.out(vs)
+
+
+def _plane2(what, **arrays):
+    """The common (Ny, Nx) of 2-D planes with Ny, Nx >= 2 (host check, before any library
+    call)."""
+    shapes = {k: tuple(np.shape(a)) for k, a in arrays.items()}
+    first = next(iter(shapes.values()))
+    if len(first) != 2 or min(first) < 2 or any(sh != first for sh in shapes.values()):
+        raise ValueError(f"{what}: (Ny, Nx) planes of one shape with Ny, Nx >= 2; got {shapes}")
+    return first
+
+
+def spline_filter_per(f):
+    """scipy.ndimage.spline_filter(f, order=3, mode='grid-wrap'): the cubic B-spline
+    coefficient plane that _interp_per evaluates (the prefilter inside mac.py:597-598)."""
+    _plane2("spline_filter_per", f=f)
+    io = _IO(f); fd = io.dev(f)
+    out = io.empty(fd.shape)
+    L.check(L.lib().rmt_mac_per_spline_prefilter(_pctx(fd.shape, True), _p(fd), _p(out)),
+            "spline_filter_per")
+    return io.out(out)
+
+
+def _interp_per(f, iq, jq):
+    """mac.py:593-598: periodic cubic interpolation of f[j, i] at the fractional indices
+    (iq, jq), arrays of one shape; the result has that shape."""
+    _plane2("_interp_per", f=f)
+    if tuple(np.shape(iq)) != tuple(np.shape(jq)):
+        raise ValueError(f"_interp_per: iq {tuple(np.shape(iq))} against jq "
+                         f"{tuple(np.shape(jq))}")
+    io = _IO(f, iq, jq); fd = io.dev(f)
+    qi = io.dev(iq).contiguous(); qj = io.dev(jq).contiguous()
+    if qi.numel() >= 2**31:
+        raise ValueError("_interp_per: fewer than 2**31 points a call")
+    out = io.empty(qi.shape)
+    L.check(L.lib().rmt_mac_per_interp(_pctx(fd.shape, True), _p(fd), _p(qi), _p(qj),
+                                       int(qi.numel()), _p(out)), "_interp_per")
+    return io.out(out)
+
+
+def _sl_advect_per(f, uf, vf, ox, oy, dx, dy, dt):
+    """mac.py:601-614: RK2 semi-Lagrangian advection of f (at offset (ox, oy) in cells) by
+    the staggered velocities uf, vf."""
+    _plane2("_sl_advect_per", f=f, uf=uf, vf=vf)
+    io = _IO(f, uf, vf); fd = io.dev(f); ud = io.dev(uf); vd = io.dev(vf)
+    out = io.empty(fd.shape)
+    L.check(L.lib().rmt_mac_per_sl_advect(_pctx(fd.shape, True), _p(fd), _p(ud), _p(vd), float(ox),
+                                          float(oy), float(dx), float(dy), float(dt), _p(out)),
+            "_sl_advect_per")
+    return io.out(out)
+
+
+def _predictor_semilag(u, v, nu, dx, dy, dt, lap_eig, cfl_switch):
+    """momentum_predictor_periodic_semilag and the branch it took: (u*, v*, took_sl)."""
+    shape = _plane2("momentum_predictor_periodic_semilag", u=u, v=v)
+    if tuple(np.shape(lap_eig)) != shape:
+        raise ValueError("momentum_predictor_periodic_semilag: the fields and lap_eig differ in "
+                         "shape")
+    lx, ly = _axis_eigs_per(lap_eig, False)
+    io = _IO(u, v); ud = io.dev(u); vd = io.dev(v)
+    us = io.empty(ud.shape); vs = io.empty(ud.shape)
+    took = ctypes.c_int(0)
+    L.check(L.lib().rmt_mac_per_predictor_semilag(
+        _pctx(ud.shape, True), _p(ud), _p(vd), float(2 * dx), float(2 * dy), float(dx), float(dy),
+        float(dt), float(dt * nu), float(cfl_switch), _hp(lx), _hp(ly), _p(us), _p(vs),
+        ctypes.byref(took)), "momentum_predictor_periodic_semilag")
+    return io.out(us), io.out(vs), bool(took.value)
+
+
+def momentum_predictor_periodic_semilag(u, v, nu, dx, dy, dt, lap_eig, cfl_switch=0.9):
+    """mac.py:617-633: momentum_predictor_periodic_imex while the advective CFL (formed on the
+    device) is at most cfl_switch, else semi-Lagrangian advection; backward-Euler viscosity
+    either way."""
+    return _predictor_semilag(u, v, nu, dx, dy, dt, lap_eig, cfl_switch)[:2]
 
 
 _PER_INTEGRATORS = {"explicit": "explicit", "exp": "explicit", "forward-euler": "explicit",
@@ -446,7 +535,8 @@ def _resolve_periodic_integrator(integrator=None, implicit_visc=False):
     key = str(integrator).lower().replace("_", "-").strip()
     if key == "imex-sl":
         raise NotImplementedError("integrator 'imex-sl' (semi-Lagrangian periodic predictor, "
-                                  "mac.py:587-633) is not built")
+                                  "mac.py:587-633) is not built as an integrator name; pass "
+                                  "semilag=True (with integrator None or 'imex')")
     if key in _ELASTIC_INTEGRATORS:
         raise ValueError("integrator='imex-elastic' is not available for this driver "
                          "(no solid-stress force path); use 'explicit' or 'imex'")
@@ -456,17 +546,34 @@ def _resolve_periodic_integrator(integrator=None, implicit_visc=False):
     return _PER_INTEGRATORS[key]
 
 
+def _resolve_periodic_semilag(integrator=None, semilag=False):
+    """The integrator behind the semilag keyword: semilag=True is the reference's "imex-sl"
+    (mac_taylor_green_convergence.py:47-49, IMEX with the semi-Lagrangian predictor), so the
+    integrator must be None or resolve to "imex"; semilag=False: _resolve_periodic_integrator."""
+    if not semilag:
+        return _resolve_periodic_integrator(integrator)
+    name = "imex" if integrator is None else _resolve_periodic_integrator(integrator)
+    if name != "imex":
+        raise ValueError(f"semilag=True is the IMEX step with semi-Lagrangian advection; "
+                         f"integrator {integrator!r} resolves to {name!r}")
+    return name
+
+
 class MacPeriodic:
     """The loop body of mac_taylor_green_convergence.py:59-66 on the GPU (rmt_mac_per_steps):
     u, v (and the last projection's phi, p) stay in HBM, a call of step(n) runs n predictor +
     projection steps at the fixed dt with no host round trip.  options: implementation
-    switches of a context of its own (macp_fused)."""
+    switches of a context of its own (macp_fused).  semilag=True: the reference's "imex-sl"
+    (rmt_mac_per_steps_sl), every step's branch decided on the device against cfl_switch;
+    sl_steps counts the steps that took the semi-Lagrangian branch."""
 
-    def __init__(self, ny, nx, dx, dy, nu, dt, rho=1.0, integrator=None, options=None):
+    def __init__(self, ny, nx, dx, dy, nu, dt, rho=1.0, integrator=None, options=None,
+                 semilag=False, cfl_switch=0.9):
+        self.integrator = _resolve_periodic_semilag(integrator, semilag)
+        self.semilag, self.cfl_switch, self.sl_steps = bool(semilag), float(cfl_switch), 0
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("pyrmt_amd needs a visible MI355X")
-        self.integrator = _resolve_periodic_integrator(integrator)
         self.torch, self.shape = torch, (int(ny), int(nx))
         self.dx, self.dy, self.nu, self.dt, self.rho = dx, dy, nu, dt, rho
         if options:
@@ -487,6 +594,17 @@ class MacPeriodic:
 
     def step(self, nsteps=1):
         dx, dy, dt = self.dx, self.dy, self.dt
+        if self.semilag:
+            took = ctypes.c_int(0)
+            L.check(L.lib().rmt_mac_per_steps_sl(
+                self.ctx.bind(), _p(self.u), _p(self.v), float(self.nu), float(dx), float(dy),
+                float(dx**2), float(dy**2), float(2 * dx), float(2 * dy), float(dt),
+                float(dt * self.nu), float(self.rho / dt), float(dt / self.rho), _hp(self.lx),
+                _hp(self.ly), self.cfl_switch, int(nsteps), _p(self.p), ctypes.byref(took)),
+                "rmt_mac_per_steps_sl")
+            self.sl_steps += took.value
+            self.nsteps += int(nsteps)
+            return
         L.check(L.lib().rmt_mac_per_steps(
             self.ctx.bind(), _p(self.u), _p(self.v), float(self.nu), float(dx), float(dy),
             float(dx**2), float(dy**2), float(2 * dx), float(2 * dy), float(dt),
@@ -518,19 +636,24 @@ def tg_exact(Xu, Yu, Xv, Yv, nu, t):
 class MacTaylorGreen(MacPeriodic):
     """The decaying Taylor-Green vortex on [0, 2 pi]^2 at N x N, rho = 1."""
 
-    def __init__(self, N, nu, dt, integrator=None, options=None):
+    def __init__(self, N, nu, dt, integrator=None, options=None, semilag=False,
+                 cfl_switch=0.9):
         dx, *self.faces = _tg_faces(N)
-        super().__init__(N, N, dx, dx, nu, dt, 1.0, integrator, options)
+        super().__init__(N, N, dx, dx, nu, dt, 1.0, integrator, options, semilag, cfl_switch)
         self.set(*tg_exact(*self.faces, nu, 0.0))
 
     def exact(self):
         return tg_exact(*self.faces, self.nu, self.nsteps * self.dt)
 
 
-def taylor_green_run_one(N, nu=0.05, T=0.2, dt=2e-4, implicit_visc=False, integrator=None):
+def taylor_green_run_one(N, nu=0.05, T=0.2, dt=2e-4, implicit_visc=False, integrator=None,
+                         semilag=False):
     """mac_taylor_green_convergence.py:39-70 (run_one): integrate to T, return (L2 error of u
-    against the exact solution, max|div|)."""
-    sim = MacTaylorGreen(N, nu, dt, _resolve_periodic_integrator(integrator, implicit_visc))
+    against the exact solution, max|div|).  semilag=True: the reference's integrator="imex-sl"."""
+    if semilag:
+        sim = MacTaylorGreen(N, nu, dt, integrator, semilag=True)
+    else:
+        sim = MacTaylorGreen(N, nu, dt, _resolve_periodic_integrator(integrator, implicit_visc))
     sim.step(int(round(T / dt)))
     ue, _ = sim.exact()
     erru = np.sqrt(np.mean((sim.get("u") - ue) ** 2))
