@@ -490,6 +490,18 @@ int rmt_mac_momentum_predictor(rmt_ctx *ctx, const double *u, const double *v, d
 int rmt_mac_contact_stress(rmt_ctx *ctx, const double *phi_a, const double *phi_b, double eta,
                            double Gsum, double eps, double dx, double dy, double *txx,
                            double *txy, double *tyy);                     /* mac.py:729-749 */
+/* The free-slip box (mac.py:653-689): rmt_mac_momentum_predictor's arithmetic with mirrored
+ * tangential ghosts (u below row 0 / above row N-1 and v beside columns 0 / N-1 are the
+ * face's own value); wall-normal faces of u_star / v_star are written as 0.  fu / fv: face
+ * forces or both NULL. */
+int rmt_mac_momentum_predictor_freeslip(rmt_ctx *ctx, const double *u, const double *v, double nu,
+                                        double dx, double dy, double dt, const double *fu,
+                                        const double *fv, double rho, double *u_star,
+                                        double *v_star);
+/* mac.py:179-193: fu (N, N+1), fv (N+1, N) = -gamma * (kappa averaged to the face) * the
+ * compact face gradient of H; every face is written, the wall faces as 0. */
+int rmt_mac_interfacial_force_faces(rmt_ctx *ctx, const double *kappa, const double *H,
+                                    double gamma, double dx, double dy, double *fu, double *fv);
 /* MAC IMEX tier (imex.hip), square N x N cell grid (ctx ny = nx = N).  kind 0: u faces, full
  * (N, N+1), interior (N, N-1); kind 1: v faces, full (N+1, N), interior (N-1, N).
  * rmt_mac_lap_lid_hom: the homogeneous-BC Laplacian of a full field on the interior faces,
@@ -543,6 +555,16 @@ typedef struct rmt_mac_sim rmt_mac_sim;
  * breaks out of its loop there); later calls are no-ops.  RMT_EDEVICE on an extrapolation
  * abort, RMT_ENONFINITE on a non-finite velocity fed to the advection. */
 int rmt_mac_sim_create(rmt_ctx *ctx, const rmt_mac_params *prm, rmt_mac_sim **out);
+/* The same loop in the free-slip box, the loop body of benchmarks/mac_disc_in_tg_convergence.py
+ * :53-82 (one disc) and mac_two_disc_contact.py:50-81 (two): wall = RMT_MAC_WALL_FREESLIP
+ * takes the predictor's ghosts of rmt_mac_momentum_predictor_freeslip (U_lid is not read).
+ * stop_on_divergence = 0: a step's record still carries diverged and the loop goes on, as
+ * those two drivers do (the two error returns of rmt_mac_sim_step stay).  Defaults: lid,
+ * stop.  Legal only before the first step (t == 0 and no record); afterwards, or with an
+ * unknown wall kind, RMT_EINVAL.  The slab path (rmt_mac_slab_*) is lid-only. */
+#define RMT_MAC_WALL_LID 0
+#define RMT_MAC_WALL_FREESLIP 1
+int rmt_mac_sim_set_mode(rmt_mac_sim *sim, int wall, int stop_on_divergence);
 int rmt_mac_sim_destroy(rmt_mac_sim *sim);
 int rmt_mac_sim_field(rmt_mac_sim *sim, int field, int disc, double **dev_ptr);
 int rmt_mac_sim_step(rmt_mac_sim *sim, int nsteps, double t_end);

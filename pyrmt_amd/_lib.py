@@ -196,6 +196,9 @@ SIGNATURES = {
     "rmt_mac_momentum_predictor_lid_semilag": (_I, [_P, _P, _P, _D, _D, _D, _D, _D, _P, _P, _D,
                                                     _D, _D, _P, _P, _P]),
     "rmt_mac_contact_stress": (_I, [_P, _P, _P, _D, _D, _D, _D, _D, _P, _P, _P]),
+    "rmt_mac_momentum_predictor_freeslip": (_I, [_P, _P, _P, _D, _D, _D, _D, _P, _P, _D, _P, _P]),
+    "rmt_mac_interfacial_force_faces": (_I, [_P, _P, _P, _D, _D, _D, _P, _P]),
+    "rmt_mac_sim_set_mode": (_I, [_P, _I, _I]),
     "rmt_mac_sim_create": (_I, [_P, ctypes.POINTER(rmt_mac_params), ctypes.POINTER(_P)]),
     "rmt_mac_sim_destroy": (_I, [_P]),
     "rmt_mac_sim_field": (_I, [_P, _I, _I, ctypes.POINTER(_P)]),

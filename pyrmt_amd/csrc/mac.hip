@@ -28,7 +28,10 @@
 //   mac_start_boxes     the call's first full pass per disc (phi, support box)
 //   per step            mac_velocity_bound, mac_disc_update per disc, mac_stress_predict,
 //                       mac_project_impl, mac_diag (the step's one sync), mac_record (host)
-// Only hbox, t, diverged and diag (rmt_mac_sim) cross steps.  The slab step (rmt_mac_slab_*,
+// Only hbox, t, diverged and diag (rmt_mac_sim) cross steps.  rmt_mac_sim_set_mode picks the
+// walls (lid cavity, or the free-slip box of benchmarks/mac_disc_in_tg_convergence.py and
+// mac_two_disc_contact.py: the predictor's ghosts are the one difference) and whether a
+// diverged record stops the loop; the slab step is lid-only.  The slab step (rmt_mac_slab_*,
 // below) runs the same kernels on row ranges and shares mac_const, mac_params_check and
 // mac_upload_coords with the fused sim.
 #include "rmt_internal.hpp"
@@ -434,13 +437,17 @@ __device__ __forceinline__ double divy_at(const double *Sxy, const double *Syy, 
 
 // mac.py:196-232 with fu / fv of mac_multi_disc_lid.py:91-94 (S == nullptr: no force).
 // Faces: u rows [F.u0, F.u1) (stride N + 1) then v rows [F.v0, F.v1) (stride N), one thread
-// each.
+// each.  WALL (rmt.h RMT_MAC_WALL_*) picks the tangential ghosts at compile time: the lid
+// cavity's (u: -u below row 0, 2U - u above row N-1; v: -v beside columns 0 and N-1) or the
+// free-slip box's mirrors (the face's own value, mac.py:661-664; U is not read).  Everything
+// else is one body: both instantiations do the same operations in the same order.
 struct FaceRows {
     int u0, u1, v0, v1;
 };
 __host__ __device__ inline long face_count(const FaceRows &F, int N) {
     return (long)(F.u1 - F.u0) * (N + 1) + (long)(F.v1 - F.v0) * N;
 }
+template <int WALL>
 __global__ void k_mac_predict(const double *__restrict__ u, const double *__restrict__ v,
                               const double *__restrict__ Sxx, const double *__restrict__ Sxy,
                               const double *__restrict__ Syy, const double *__restrict__ fu,
@@ -456,8 +463,10 @@ __global__ void k_mac_predict(const double *__restrict__ u, const double *__rest
         const int j = dv32(q, W), i = (int)(q - (long)j * W);
         if (i == 0 || i == N) { us[q] = 0.0; return; }
         const double uc = u[q], ul = u[q - 1], ur = u[q + 1];
-        const double dn = j > 0 ? u[q - W] : -u[q];                 // ghost: -u[0]
-        const double up = j < N - 1 ? u[q + W] : 2.0 * U - u[q];    // ghost: 2U - u[-1]
+        constexpr bool FS = WALL == RMT_MAC_WALL_FREESLIP;
+        const double dn = j > 0 ? u[q - W] : (FS ? u[q] : -u[q]);   // ghost: -u[0] (FS: u[0])
+        // ghost: 2U - u[-1] (FS: u[-1])
+        const double up = j < N - 1 ? u[q + W] : (FS ? u[q] : 2.0 * U - u[q]);
         const double dudx = (ur - ul) / (2 * dx);
         const double dudy = (up - dn) / (2 * dy);
         const double lap = (ur - 2 * uc + ul) / dx2 + (up - 2 * uc + dn) / dy2;
@@ -474,8 +483,9 @@ __global__ void k_mac_predict(const double *__restrict__ u, const double *__rest
         const int j = dv32(p, N), i = (int)(p - (long)j * N);
         if (j == 0 || j == N) { vs[p] = 0.0; return; }
         const double vc = v[p], vd = v[p - N], vup = v[p + N];
-        const double vl = i > 0 ? v[p - 1] : -v[p];
-        const double vr = i < N - 1 ? v[p + 1] : -v[p];
+        constexpr bool FS = WALL == RMT_MAC_WALL_FREESLIP;
+        const double vl = i > 0 ? v[p - 1] : (FS ? v[p] : -v[p]);
+        const double vr = i < N - 1 ? v[p + 1] : (FS ? v[p] : -v[p]);
         const double dvdx = (vr - vl) / (2 * dx);
         const double dvdy = (vup - vd) / (2 * dy);
         const double lap = (vr - 2 * vc + vl) / dx2 + (vup - 2 * vc + vd) / dy2;
@@ -486,6 +496,29 @@ __global__ void k_mac_predict(const double *__restrict__ u, const double *__rest
         else if (Sxx) r = r + 0.5 * (divy_at(Sxy, Syy, j, i, N, dx, dy) + divy_at(Sxy, Syy, j - 1, i, N, dx, dy)) / rho;
         else if (fv) r = r + fv[p] / rho;
         vs[p] = vc + dt * r;
+    }
+}
+
+// mac.py:179-193 interfacial_force_faces: f = -gamma * kappa_face * grad(H) with the compact
+// face gradient of k_mac_correct; one thread per face, the u faces then the v faces; wall
+// faces are written as 0 (the planes come in uninitialised)
+__global__ void k_mac_face_force(const double *__restrict__ kap, const double *__restrict__ H,
+                                 int N, double gamma, double dx, double dy,
+                                 double *__restrict__ fu, double *__restrict__ fv) {
+    const long t = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    const long nuf = (long)N * (N + 1);
+    if (t < nuf) {   // u face (j, i) between cells (j, i - 1) and (j, i)
+        const int j = dv32(t, N + 1), i = (int)(t - (long)j * (N + 1));
+        if (i == 0 || i == N) { fu[t] = 0.0; return; }
+        const long c = (long)j * N + i;
+        const double ku = 0.5 * (kap[c] + kap[c - 1]);
+        fu[t] = -gamma * ku * (H[c] - H[c - 1]) / dx;
+    } else if (t < 2 * nuf) {   // v face (j, i) between cells (j - 1, i) and (j, i)
+        const long p = t - nuf;
+        const int j = dv32(p, N);
+        if (j == 0 || j == N) { fv[p] = 0.0; return; }
+        const double kv = 0.5 * (kap[p] + kap[p - N]);
+        fv[p] = -gamma * kv * (H[p] - H[p - N]) / dy;
     }
 }
 
@@ -770,6 +803,9 @@ struct rmt_mac_sim {
     int fl[4];                    // non-finite centre, non-finite sample, fitted, sweep aborted
     double t = 0;
     bool diverged = false;
+    // rmt_mac_sim_set_mode: the predictor's wall ghosts; whether a diverged record stops the loop
+    int wall = RMT_MAC_WALL_LID;
+    bool stop = true;
     std::vector<rmt_mac_diag> diag;
 };
 
@@ -936,9 +972,15 @@ static int mac_stress_predict(rmt_mac_sim *S, const MacSched &sc, const DiscSet 
     RMT_LAUNCHED();
     RMT_HIP(hipMemcpyAsync(S->jr.data(), S->part, 2 * sc.npart() * sizeof(double),
                            hipMemcpyDeviceToHost, st));
-    k_mac_predict<<<grid1d(2 * (long)N * (N + 1), 256), 256, 0, st>>>(
-        S->u, S->v, S->Sxx, S->Sxy, S->Syy, nullptr, nullptr, N, sc.nu, sc.dx, sc.dx, sc.dx2,
-        sc.dx2, dt, P.U_lid, P.rho, S->us, S->vs, FaceRows{0, N, 0, N + 1}, D.bx);
+    const dim3 pg = grid1d(2 * (long)N * (N + 1), 256);
+    if (S->wall == RMT_MAC_WALL_FREESLIP)   // (U_lid is not read)
+        k_mac_predict<RMT_MAC_WALL_FREESLIP><<<pg, 256, 0, st>>>(
+            S->u, S->v, S->Sxx, S->Sxy, S->Syy, nullptr, nullptr, N, sc.nu, sc.dx, sc.dx, sc.dx2,
+            sc.dx2, dt, 0.0, P.rho, S->us, S->vs, FaceRows{0, N, 0, N + 1}, D.bx);
+    else
+        k_mac_predict<RMT_MAC_WALL_LID><<<pg, 256, 0, st>>>(
+            S->u, S->v, S->Sxx, S->Sxy, S->Syy, nullptr, nullptr, N, sc.nu, sc.dx, sc.dx, sc.dx2,
+            sc.dx2, dt, P.U_lid, P.rho, S->us, S->vs, FaceRows{0, N, 0, N + 1}, D.bx);
     RMT_LAUNCHED();
     return RMT_OK;
 }
@@ -995,7 +1037,7 @@ static int mac_record(rmt_mac_sim *S, const MacSched &sc, double dt) {
     for (int k = 0; k < sc.K; ++k) lost |= !(acc[3 * k + 2] > 0);
     r.diverged = !std::isfinite(r.umax) || r.minJ < 0.0 || r.maxJ > 20.0 || lost;
     S->diag.push_back(r);
-    S->diverged = r.diverged;   // (the loop stops ahead of the next step)
+    S->diverged = r.diverged;   // (the loop stops ahead of the next step, unless stop is off)
     return RMT_OK;
 }
 
@@ -1053,9 +1095,33 @@ int rmt_mac_momentum_predictor(rmt_ctx *ctx, const double *u, const double *v, d
     RMT_CHECK(!fu == !fv, RMT_EINVAL, "give both face forces or neither");
     const int N = ctx->nx;
     const long nf = (long)N * (N + 1);
-    k_mac_predict<<<grid1d(2 * nf, 256), 256, 0, ctx->stream>>>(
+    k_mac_predict<RMT_MAC_WALL_LID><<<grid1d(2 * nf, 256), 256, 0, ctx->stream>>>(
         u, v, nullptr, nullptr, nullptr, fu, fv, N, nu, dx, dy, std::pow(dx, 2.0),
         std::pow(dy, 2.0), dt, U_lid, rho, us, vs, FaceRows{0, N, 0, N + 1});
+    RMT_LAUNCHED();
+    return RMT_OK;
+}
+
+int rmt_mac_momentum_predictor_freeslip(rmt_ctx *ctx, const double *u, const double *v, double nu,
+                                        double dx, double dy, double dt, const double *fu,
+                                        const double *fv, double rho, double *us, double *vs) {
+    RMT_CHECK(ctx && u && v && us && vs && ctx->nx == ctx->ny, RMT_EINVAL, "bad argument");
+    RMT_CHECK(!fu == !fv, RMT_EINVAL, "give both face forces or neither");
+    const int N = ctx->nx;
+    const long nf = (long)N * (N + 1);
+    k_mac_predict<RMT_MAC_WALL_FREESLIP><<<grid1d(2 * nf, 256), 256, 0, ctx->stream>>>(
+        u, v, nullptr, nullptr, nullptr, fu, fv, N, nu, dx, dy, std::pow(dx, 2.0),
+        std::pow(dy, 2.0), dt, 0.0, rho, us, vs, FaceRows{0, N, 0, N + 1});
+    RMT_LAUNCHED();
+    return RMT_OK;
+}
+
+int rmt_mac_interfacial_force_faces(rmt_ctx *ctx, const double *kappa, const double *H,
+                                    double gamma, double dx, double dy, double *fu, double *fv) {
+    RMT_CHECK(ctx && kappa && H && fu && fv && ctx->nx == ctx->ny, RMT_EINVAL, "bad argument");
+    const int N = ctx->nx;
+    k_mac_face_force<<<grid1d(2 * (long)N * (N + 1), 256), 256, 0, ctx->stream>>>(
+        kappa, H, N, gamma, dx, dy, fu, fv);
     RMT_LAUNCHED();
     return RMT_OK;
 }
@@ -1138,15 +1204,28 @@ int rmt_mac_sim_field(rmt_mac_sim *S, int field, int disc, double **ptr) {
     return RMT_OK;
 }
 
+int rmt_mac_sim_set_mode(rmt_mac_sim *S, int wall, int stop_on_divergence) {
+    RMT_CHECK(S, RMT_EINVAL, "null sim");
+    RMT_CHECK(wall == RMT_MAC_WALL_LID || wall == RMT_MAC_WALL_FREESLIP, RMT_EINVAL,
+              "unknown wall kind");
+    RMT_CHECK(S->t == 0 && S->diag.empty(), RMT_EINVAL,
+              "rmt_mac_sim_set_mode: only before the first step");
+    S->wall = wall;
+    S->stop = stop_on_divergence != 0;
+    return RMT_OK;
+}
+
 int rmt_mac_sim_step(rmt_mac_sim *S, int nsteps, double t_end) {
     RMT_CHECK(S, RMT_EINVAL, "null sim");
     const rmt_mac_params &P = S->P;
     const MacSched sc = mac_sched(S);
     DiscSet D = mac_discs(S, sc);
-    if (sc.box_mode && nsteps > 0 && S->t < t_end && !S->diverged)
+    // (stop off: a diverged record does not end the loop, as the free-slip drivers go on)
+    const auto halted = [S] { return S->diverged && S->stop; };
+    if (sc.box_mode && nsteps > 0 && S->t < t_end && !halted())
         RMT_TRY(mac_start_boxes(S, sc));
     for (int it = 0; it < nsteps; ++it) {
-        if (!(S->t < t_end) || S->diverged) break;
+        if (!(S->t < t_end) || halted()) break;
         double dt = P.dt;
         if (S->t + dt > t_end) dt = t_end - S->t;
         RMT_TRY(mac_velocity_bound(S, sc, it));
@@ -1458,7 +1537,7 @@ int rmt_mac_slab_predict(rmt_mac_slab *S, double dt) {
         stress_skip_ok(P));
     RMT_LAUNCHED();
     const FaceRows F{S->r0, S->r1, S->r0, std::min(S->r1 + 1, N + 1)};
-    k_mac_predict<<<grid1d(face_count(F, N), 256), 256, 0, ctx->stream>>>(
+    k_mac_predict<RMT_MAC_WALL_LID><<<grid1d(face_count(F, N), 256), 256, 0, ctx->stream>>>(
         S->gu(S->u), S->gc(S->v), S->gc(S->Sxx), S->gc(S->Sxy), S->gc(S->Syy), nullptr, nullptr,
         N, c.nu, dx, dx, c.dx2, c.dx2, dt, P.U_lid, P.rho, S->gu(S->us), S->gc(S->vs), F);
     RMT_LAUNCHED();

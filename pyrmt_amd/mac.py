@@ -9,6 +9,11 @@ benchmarks/mac_multi_disc_lid.py:36-98 (K soft discs with pair contact).
 The periodic tier (mac.py:445-540, 587-650; rmt_mac_per_*) keeps u, v and p all (Ny, Nx);
 ``MacTaylorGreen`` / ``taylor_green_run_one`` are benchmarks/mac_taylor_green_convergence.py,
 its semi-Lagrangian integrator behind ``semilag=True``.
+The free-slip box (mac.py:179-193, 656-689): ``momentum_predictor_freeslip``,
+``interfacial_force_faces``, and the same fused loop with free-slip walls behind
+``MacMultiDisc(walls="freeslip")``: ``MacDiscTaylorGreen`` / ``disc_in_tg_run_one``
+(benchmarks/mac_disc_in_tg_convergence.py) and ``MacTwoDiscContact``
+(benchmarks/mac_two_disc_contact.py).
 """
 import ctypes
 import math
@@ -275,6 +280,32 @@ def momentum_predictor_lid_semilag(u, v, nu, dx, dy, dt, U_lid, fu=None, fv=None
     return io.out(us), io.out(vs)
 
 
+def momentum_predictor_freeslip(u, v, nu, dx, dy, dt, fu=None, fv=None, rho=1.0):
+    """mac.py:656-689: the explicit predictor on the free-slip box (mirrored tangential
+    ghosts, wall-normal faces zeroed)."""
+    if (fu is None) != (fv is None):
+        raise NotImplementedError("momentum_predictor_freeslip: give both face forces or neither")
+    N = _lid_n("momentum_predictor_freeslip", u, v, fu, fv)
+    io = _IO(u, v); ud = io.dev(u); vd = io.dev(v)
+    fud, fvd = io.dev(fu), io.dev(fv)
+    us = io.empty(ud.shape); vs = io.empty(vd.shape)
+    # (N = 4, below the stencil contexts' 5: a context of its own, as the periodic tier's)
+    L.check(L.lib().rmt_mac_momentum_predictor_freeslip(
+        _pctx((N, N), True), _p(ud), _p(vd), nu, dx, dy, dt, _p(fud), _p(fvd), float(rho), _p(us), _p(vs)),
+        "momentum_predictor_freeslip")
+    return io.out(us), io.out(vs)
+
+
+def interfacial_force_faces(kappa, H, gamma, dx, dy):
+    """mac.py:179-193: the balanced continuum-surface force on the faces, (fu, fv)."""
+    N = _lid_n("interfacial_force_faces", kappa=kappa, H=H)
+    io = _IO(kappa, H); kd = io.dev(kappa); Hd = io.dev(H)
+    fu = io.empty((N, N + 1)); fv = io.empty((N + 1, N))
+    L.check(L.lib().rmt_mac_interfacial_force_faces(_pctx((N, N), True), _p(kd), _p(Hd), gamma, dx, dy,
+                                                    _p(fu), _p(fv)), "interfacial_force_faces")
+    return io.out(fu), io.out(fv)
+
+
 def contact_stress(phi_a, phi_b, eta, Gsum, eps, dx, dy):
     """mac.py:729-749: (txx, txy, tyy)."""
     N = _lid_n("contact_stress", phi_a=phi_a, phi_b=phi_b)
@@ -291,8 +322,7 @@ def contact_stress(phi_a, phi_b, eta, Gsum, eps, dx, dy):
 # bit-exact; the solves go through rocFFT on the half-spectrum (the reference: numpy.fft) and
 # the grid-wrap cubic splines of the semi-Lagrangian predictor through a windowed prefilter
 # (the reference: scipy.ndimage), both equal to rounding.  Not covered:
-# momentum_predictor_periodic_imex_elastic, momentum_predictor_freeslip,
-# advect_xi_conservative, interfacial_force_faces.
+# momentum_predictor_periodic_imex_elastic, advect_xi_conservative.
 _small_ctxs = {}
 
 
@@ -676,14 +706,16 @@ def place_discs(n, seed, Rrange=(0.07, 0.12), box=(0.18, 0.82)):
     return discs
 
 
-def mac_params(N, specs, U_lid=1.0, mu_s=0.3, mu_f=0.01, rho=1.0, eta=2.0):
-    """rmt_mac_params and the fixed dt of mac_multi_disc_lid.py:36-60."""
+def mac_params(N, specs, U_lid=1.0, mu_s=0.3, mu_f=0.01, rho=1.0, eta=2.0, dt=None):
+    """rmt_mac_params and the fixed dt of mac_multi_disc_lid.py:36-60 (dt given: that step in
+    the formula's place, which a free-slip box with U_lid = 0 has no use for)."""
     dx, _ = mac_grid(N, N)
     specs = list(specs)
     if not 1 <= len(specs) <= 8:
         raise ValueError("1..8 discs")
     cs = np.sqrt(mu_s / rho)
-    dt = min(0.3 * dx / U_lid, 0.2 * dx * dx / (mu_f / rho), 0.3 * dx / (cs + 1e-9))
+    if dt is None:
+        dt = min(0.3 * dx / U_lid, 0.2 * dx * dx / (mu_f / rho), 0.3 * dx / (cs + 1e-9))
     P = L.rmt_mac_params()
     P.N = N; P.dx = dx; P.n_discs = len(specs)
     for k, (R, cx, cy) in enumerate(specs):
@@ -713,9 +745,19 @@ class MacMultiDisc:
     every disc's X1, X2, phi) stays in HBM; one host sync per step reads the diagnostics."""
 
     FIELDS = {"u": 0, "v": 1, "p": 2, "X1": 3, "X2": 4, "phi": 5}
+    WALLS = {"lid": 0, "freeslip": 1}   # RMT_MAC_WALL_*
 
     def __init__(self, N=128, n_discs=3, seed=3, U_lid=1.0, mu_s=0.3, mu_f=0.01, rho=1.0,
-                 eta=2.0, specs=None, options=None):
+                 eta=2.0, specs=None, options=None, walls="lid", stop_on_divergence=True,
+                 dt=None):
+        """walls: "lid" (the cavity, U_lid) or "freeslip" (the box of
+        mac_disc_in_tg_convergence.py / mac_two_disc_contact.py; U_lid is not read);
+        stop_on_divergence=False: the loop goes on past a record with diverged set, as those
+        two drivers do; dt: a fixed step in place of mac_params' formula."""
+        if walls not in self.WALLS:
+            raise ValueError(f"walls {walls!r}: one of {tuple(self.WALLS)}")
+        if dt is not None and not (float(dt) > 0.0 and math.isfinite(float(dt))):
+            raise ValueError(f"dt {dt!r}: a positive finite step")
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("pyrmt_amd needs a visible MI355X")
@@ -725,7 +767,7 @@ class MacMultiDisc:
         self.specs = list(specs) if specs is not None else place_discs(n_discs, seed)
         if not 1 <= len(self.specs) <= 8:
             raise ValueError("1..8 discs")
-        P, self.dt = mac_params(N, self.specs, U_lid, mu_s, mu_f, rho, eta)
+        P, self.dt = mac_params(N, self.specs, U_lid, mu_s, mu_f, rho, eta, dt)
         if options:
             # a context of its own with these implementation switches (rmt_ctx_set_option)
             from .functions import _Ctx
@@ -738,6 +780,9 @@ class MacMultiDisc:
         L.check(L.lib().rmt_mac_sim_create(self.ctx.bind(), ctypes.byref(P), ctypes.byref(h)),
                 "rmt_mac_sim_create")
         self.h, self.params = h, P
+        self.walls, self.stop_on_divergence = walls, bool(stop_on_divergence)
+        if walls != "lid" or not stop_on_divergence:
+            self.set_mode(walls, stop_on_divergence)
         self._views = {}
         # the initial maps go up through one pinned staging plane: a DMA copy per map instead of
         # the runtime's pageable staging (≈0.6 MB chunks: ~7,800 copies at N=8192)
@@ -754,6 +799,12 @@ class MacMultiDisc:
             L.lib().rmt_mac_sim_destroy(self.h)
         except Exception:
             pass
+
+    def set_mode(self, walls, stop_on_divergence):
+        """rmt_mac_sim_set_mode: legal only before the first step."""
+        L.check(L.lib().rmt_mac_sim_set_mode(self.h, self.WALLS[walls], int(bool(stop_on_divergence))),
+                "rmt_mac_sim_set_mode")
+        self.walls, self.stop_on_divergence = walls, bool(stop_on_divergence)
 
     def field(self, name, disc=0):
         key = (name, disc if name in ("X1", "X2", "phi") else 0)
@@ -785,3 +836,110 @@ class MacMultiDisc:
         out["cx"] = np.array([[buf[i].cx[k] for k in range(K)] for i in range(n.value)])
         out["cy"] = np.array([[buf[i].cy[k] for k in range(K)] for i in range(n.value)])
         return out
+
+
+# ------------------------------------------------------------------ free-slip box --
+def disc_in_tg_dt(N, mu_s=0.1, mu_f=0.01, U0=0.3, rho=1.0):
+    """mac_disc_in_tg_convergence.py:47-49 (setup, host): the driver's fixed step."""
+    dx, _ = mac_grid(N, N)
+    nu = mu_f / rho; cs = np.sqrt(mu_s / rho)
+    return float(min(0.25 * dx / (U0 * np.pi), 0.2 * dx * dx / nu, 0.25 * dx / (cs + 1e-9)))
+
+
+def two_disc_dt(N, V0=0.3, mu_s=0.2, mu_f=0.02, rho=1.0):
+    """mac_two_disc_contact.py:36-45 (setup, host): the driver's fixed step."""
+    dx, _ = mac_grid(N, N)
+    nu = mu_f / rho; cs = np.sqrt(mu_s / rho)
+    return float(min(0.25 * dx / max(V0, 1e-9), 0.2 * dx * dx / nu, 0.25 * dx / (cs + 1e-9)))
+
+
+class MacDiscTaylorGreen(MacMultiDisc):
+    """benchmarks/mac_disc_in_tg_convergence.py:30-82 (run_one, scheme "semilagrangian") on the
+    GPU: a neo-Hookean disc in the decaying Taylor-Green vortex psi = U0 sin(pi x) sin(pi y)
+    on the free-slip box; the loop runs past a folded map, as the driver does."""
+
+    def __init__(self, N, R=0.15, x0=0.5, y0=0.7, mu_s=0.1, mu_f=0.01, U0=0.3, rho=1.0,
+                 options=None):
+        super().__init__(N, specs=[(R, x0, y0)], U_lid=0.0, mu_s=mu_s, mu_f=mu_f, rho=rho,
+                         eta=0.0, options=options, walls="freeslip", stop_on_divergence=False,
+                         dt=disc_in_tg_dt(N, mu_s, mu_f, U0, rho))
+        self.mu_s, self.U0 = mu_s, U0
+        dx = self.dx
+        xc = (np.arange(N) + 0.5) * dx; xf = np.arange(N + 1) * dx
+        Xu, Yu = np.meshgrid(xf, xc)
+        Xv, Yv = np.meshgrid(xc, xf)
+        u = U0 * np.pi * np.sin(np.pi * Xu) * np.cos(np.pi * Yu)       # :40-42
+        v = -U0 * np.pi * np.cos(np.pi * Xv) * np.sin(np.pi * Yv)
+        u[:, 0] = 0.0; u[:, -1] = 0.0; v[0, :] = 0.0; v[-1, :] = 0.0
+        self.field("u").copy_(self.torch.from_numpy(u))
+        self.field("v").copy_(self.torch.from_numpy(v))
+        self.torch.cuda.synchronize()
+
+
+def disc_in_tg_run_one(N, t_end, R=0.15, x0=0.5, y0=0.7, mu_s=0.1, mu_f=0.01, U0=0.3, rho=1.0,
+                       scheme="semilagrangian", w_cut_fac=4.0, isochoric=False,
+                       normalize_phi=False):
+    """mac_disc_in_tg_convergence.py:30-91 (run_one): the dict N, dx, xc, speed, p, KE,
+    Estrain, divmax at t_end.  w_cut_fac is accepted and ignored, as the semi-Lagrangian
+    advection ignores w_cut (functions.py:528-529)."""
+    if scheme != "semilagrangian" or isochoric or normalize_phi:
+        raise NotImplementedError(
+            "disc_in_tg_run_one: the fused loop runs scheme='semilagrangian' with "
+            "isochoric=False and normalize_phi=False; the other variants can be composed from "
+            "functions.advect_reference_map, functions.extrapolate_reference_map, "
+            "functions.solid_cauchy_stress, functions.smoothed_heaviside, "
+            "mac.momentum_predictor_freeslip and mac.project")
+    return _disc_in_tg_run(N, t_end, R, x0, y0, mu_s, mu_f, U0, rho)[1]
+
+
+def _disc_in_tg_run(N, t_end, R=0.15, x0=0.5, y0=0.7, mu_s=0.1, mu_f=0.01, U0=0.3, rho=1.0,
+                    options=None):
+    """(sim, run_one's dict): the loop to t_end (the last step truncated, :54-55), then the
+    end-of-run measures of :84-91."""
+    from .functions import compute_strain_energy
+    if not math.isfinite(t_end):
+        raise ValueError("disc_in_tg_run_one: a finite t_end")
+    sim = MacDiscTaylorGreen(N, R, x0, y0, mu_s, mu_f, U0, rho, options=options)
+    sim.step(2**31 - 1, t_end)   # (the loop ends at t_end)
+    dx = sim.dx
+    u, v = sim.field("u"), sim.field("v")
+    u_c = 0.5 * (u[:, :-1] + u[:, 1:]); v_c = 0.5 * (v[:-1, :] + v[1:, :])
+    sq = (u_c**2 + v_c**2).cpu().numpy()
+    KE = 0.5 * np.sum(sq) * dx * dx
+    # (the reference's compute_strain_energy returns the integrated scalar; the driver's
+    # finite-only sum and second dx * dy factor are kept as they are, :87-88)
+    se = compute_strain_energy(sim.field("X1"), sim.field("X2"), sim.field("phi"), mu_s, dx, dx)
+    Estrain = np.nansum(np.where(np.isfinite(se), se, 0.0)) * dx * dx
+    divmax = float(divergence(u, v, dx, dx).abs().max())
+    return sim, dict(N=N, dx=dx, xc=(np.arange(N) + 0.5) * dx, speed=np.sqrt(sq), p=sim.get("p"),
+                     KE=KE, Estrain=Estrain, divmax=divmax)
+
+
+class MacTwoDiscContact(MacMultiDisc):
+    """benchmarks/mac_two_disc_contact.py:21-84 on the GPU: two discs driven into each other
+    on the free-slip box, rebounding through the contact stress (eta)."""
+
+    def __init__(self, N=128, V0=0.3, eta=2.0, mu_s=0.2, mu_f=0.02, rho=1.0, R=0.12, sep=0.36,
+                 options=None):
+        from .functions import smoothed_heaviside
+        xa, xb, yc0 = 0.5 - sep / 2, 0.5 + sep / 2, 0.5
+        super().__init__(N, specs=[(R, xa, yc0), (R, xb, yc0)], U_lid=0.0, mu_s=mu_s, mu_f=mu_f,
+                         rho=rho, eta=eta, options=options, walls="freeslip",
+                         stop_on_divergence=False, dt=two_disc_dt(N, V0, mu_s, mu_f, rho))
+        self.V0, self.R = V0, R
+        dx = self.dx
+        xc = (np.arange(N) + 0.5) * dx; xf = np.arange(N + 1) * dx
+        Xu, Yu = np.meshgrid(xf, xc)
+        w_t = 2.0 * dx
+        HaU = np.asarray(smoothed_heaviside(np.sqrt((Xu - xa)**2 + (Yu - yc0)**2) - R, w_t))
+        HbU = np.asarray(smoothed_heaviside(np.sqrt((Xu - xb)**2 + (Yu - yc0)**2) - R, w_t))
+        u = V0 * (1 - HaU) - V0 * (1 - HbU)                            # :38-42
+        u[:, 0] = 0; u[:, -1] = 0
+        self.field("u").copy_(self.torch.from_numpy(u))
+        self.torch.cuda.synchronize()
+
+    def history(self):
+        """The (t, cxA, cxB, gap) rows the driver's run returns (:82-84, 89)."""
+        d = self.diagnostics()
+        cx = d["cx"].reshape(-1, 2)
+        return np.column_stack([d["t"], cx[:, 0], cx[:, 1], cx[:, 1] - cx[:, 0]])
