@@ -80,7 +80,8 @@ int rmt_ctx_kernel_ms(rmt_ctx *ctx, double *ms2);
  * variable at rmt_ctx_create.  Names: ext_events, ex_arena_bump, ex_profile, fix_all,
  * dct_rocfft, transpose2, sim_hiprio, sim_sync, early_geometry, early_transpose, fused_fluid,
  * no_overlap, side_tail, par_overlap, fused_fixprep, merged_join, test_delay_side,
- * test_delay_main, chain_cols, chain_layer_groups, edge_slots, edge_stream, sl_phi,
+ * test_delay_main, chain_cols, chain_layer_groups, chain_waves (8 or 16 waves per chain
+ * workgroup; any other value: RMT_EINVAL), edge_slots, edge_stream, sl_phi,
  * mac_boxes, skip_marked_rows, tail_stream, diag_first, mac_noop_host, mac_face_sl,
  * mac_m2_bound, diag_seg, sl_zero_flags, macp_fused (rmt_mac_per_steps' explicit step: the
  * predictor and the divergence in one kernel, same bits), dct_sym (read when the context's DCT

@@ -10,10 +10,8 @@ typedef unsigned long long u64;
 
 constexpr int EX_MAXL = 8;          // layers the chain path handles (more -> fallback sweep)
 constexpr int CH_R = 2048;          // chain value ring (slots, chain order); deps < CH_R/2 back
-#ifndef RMT_CH_W
-#define RMT_CH_W 16
-#endif
-constexpr int CH_W = RMT_CH_W;      // chain workgroup waves (4 per SIMD)
+constexpr int CH_W = 16;            // chain workgroup waves at most (4 per SIMD); a call runs
+                                    // rmt_opts::ch_waves of them (8 or 16: ctl[EXC_NW])
 constexpr int CH_HDR = 24;          // record header, doubles
 constexpr int CH_TVS = 88;          // padded fold terms per sum (81 rounded up to 8)
 constexpr int CH_MAXREC = 8 * (CH_HDR + 6 * CH_TVS + 4 * 64);   // 6464 B (<= 64 sources)
@@ -35,6 +33,7 @@ enum { EXC_FALLBACK = 0, EXC_ABORT = 1, EXC_FILLED = 2, EXC_ARENA = 4, EXC_REJ =
        EXC_WSTART = EXC_NPART + CH_MAXP + 1,                // + p * CH_W + w: wave w's first
        EXC_NCOL = EXC_WSTART + CH_MAXP * CH_W,              // ordinal in part p
        EXC_NLG = EXC_NCOL + 1,
+       EXC_NW = EXC_NLG + 1,                                // waves per part of this call
        EXC_WORDS = EXC_NLG + 8 };
 // cross-part hand-off granules (gval) hold this signalling NaN until the fit is published: an
 // arithmetic result is never a signalling NaN (IEEE mode), so the value is its own flag

@@ -20,7 +20,8 @@
 //   2. chain order (k_ex_order/chainidx/relink): fits are numbered in order of (j + 5L, L, i),
 //      a topological order of the true dependency DAG (a layer-L fit reads layer L rows j-4..j
 //      and layer L-1 rows j-4..j+4), and record sources are rewritten to chain indices.
-//   3. k_ex_chain, one workgroup: waves take chain indices round-robin; a fit waits for its
+//   3. k_ex_chain, one workgroup per chain part (column range x layer group) of 8 or 16
+//      waves: the waves take the part's fits round-robin; a fit waits for its
 //      dynamic sources in an LDS value ring (tag == chain index), forms their products, folds
 //      the 6 ordered sums over its record terms (lanes 0-5) and runs the 3x3 solve of
 //      utils.py:134-166 with the precomputed cofactors -- the same operations, in the same
@@ -550,7 +551,8 @@ __global__ void __launch_bounds__(1024) k_ex_order(ExWs ws, int ny, int ML) {
 // chain parts: split column = middle of the targets' column range (ncol == 2), so the two
 // sides of the band run apart; the few fits near the split column hand their values across
 // through L2 / the fabric, as every fit read by a later layer group does
-__global__ void __launch_bounds__(1024) k_ex_split(ExWs ws, int nx, int ML, int ncol, int nlg) {
+__global__ void __launch_bounds__(1024) k_ex_split(ExWs ws, int nx, int ML, int ncol, int nlg,
+                                                   int nw) {
     __shared__ int smin[1024], smax[1024];
     const int t = threadIdx.x, total = ws.ctl[EXC_BASE + ML];
     int mn = 0x7fffffff, mx = -1;
@@ -569,6 +571,7 @@ __global__ void __launch_bounds__(1024) k_ex_split(ExWs ws, int nx, int ML, int 
         ws.ctl[EXC_CMAX] = smax[0] >= smin[0] ? smax[0] - smin[0] + 1 : 1;   // span
         ws.ctl[EXC_NCOL] = ncol;
         ws.ctl[EXC_NLG] = nlg;
+        ws.ctl[EXC_NW] = nw;
         ws.ctl[EXC_NPART + CH_MAXP] = ncol * nlg;
     }
 }
@@ -662,7 +665,8 @@ __device__ __forceinline__ int ch_base(const int *ctl, int p) {
     return b;
 }
 
-// Wave assignment of part blockIdx.x: ordinal l on wave l % CH_W (round robin: a fit's record
+// Wave assignment of part blockIdx.x: ordinal l on wave l % W, W = ctl[EXC_NW] waves per part
+// (k_ex_split; the table of first ordinals keeps its stride CH_W) (round robin: a fit's record
 // staging and prefix fold overlap its predecessors' waits; giving each row run of fits to one
 // wave measured slower in round 3, 4.32 vs 3.0 ms at N=4096).  One block per part.
 __global__ void __launch_bounds__(1024) k_ex_runs(ExWs ws) {
@@ -670,9 +674,10 @@ __global__ void __launch_bounds__(1024) k_ex_runs(ExWs ws) {
     const int p = blockIdx.x, t = threadIdx.x;
     if (p >= ws.ctl[EXC_NPART + CH_MAXP]) return;
     const int np = ws.ctl[EXC_NPART + p], base = ch_base(ws.ctl, p);
+    const int W = ws.ctl[EXC_NW];
     int *wst = ws.ctl + EXC_WSTART + p * CH_W;
-    for (int l = t; l < np; l += 1024) ws.wnext[base + l] = l + CH_W;
-    if (t < CH_W) wst[t] = min(t, np);
+    for (int l = t; l < np; l += 1024) ws.wnext[base + l] = l + W;
+    if (t < W) wst[t] = min(t, np);
 }
 
 // record sources: fit ids -> ring tags within the fit's part (the ring needs every source
@@ -741,8 +746,31 @@ constexpr int CH_XL2 = 3;   // the lane of a fit's X2 result (ch_fit)
 #ifndef RMT_CH_ABL
 #define RMT_CH_ABL 0   // timing ablations (wrong results, A/B only): 1 no tail fold, 2 no
 #endif                 // solve, 4 no waits for sources
-constexpr int CH_BUFD = CH_MAXREC / 8 + 32;   // doubles per wave record buffer (+ the tail
-                                              // prefetch's NRT = 24 reads past a short record)
+// Register tail of a fit (ch_fit): the terms after its critical one that are read into
+// registers before the critical value arrives.  16 waves per part leave 128 VGPRs a wave: 24
+// terms (8 in the profiled build, whose counters need the registers), the rest from LDS after
+// the arrival (ch_fold).  8 waves leave 256: the whole tail, in both builds.  The tail starts
+// at chunk h0 = (kc + 1) >> 3 of the record's npad padded terms.  ex_geom gives the critical
+// term kc no lower bound (the first dynamic cell of the window, term 0, is the critical one
+// whenever every other source lies in another part), so the earliest tail chunk is 0; and a
+// record holds at most CH_NMAX = 80 terms, the 81 window cells less the target's own (a
+// target is unknown before its layer, and a same-layer cell is included only from an earlier
+// raster position), which are whole chunks: the whole tail is at most 80 terms.  (ch_fit
+// refuses a longer record at 8 waves like any other malformed one.)
+constexpr int CH_NMAX = 81 - 1;
+template <bool PROF, int W> constexpr int ch_nrt() {
+    return W == 8 ? (CH_NMAX + 7) / 8 * 8 : (PROF ? 8 : 24);
+}
+static_assert(ch_nrt<false, 8>() == ch_nrt<true, 8>() && ch_nrt<false, 8>() >= CH_NMAX &&
+              ch_nrt<false, 8>() <= CH_TVS,
+              "8 waves: no record leaves tail terms in LDS, and the trace build matches");
+static_assert(ch_nrt<false, 16>() == 24 && ch_nrt<true, 16>() == 8, "16 waves: as tuned");
+// doubles per wave record buffer (+ the tail prefetch's NRT reads past a short record, rounded
+// up to 32)
+template <int W> constexpr int ch_bufd() {
+    return CH_MAXREC / 8 + (ch_nrt<false, W>() + 31) / 32 * 32;
+}
+static_assert(ch_bufd<16>() == CH_MAXREC / 8 + 32 && ch_bufd<8>() % 2 == 0, "16-B aligned rows");
 constexpr long CH_SPIN_LIMIT = 1L << 25;
 
 struct ChainArgs {
@@ -785,8 +813,19 @@ struct ChainArgs {
 #define CH_STAMP(k)                                                    \
     if constexpr (PROF) {                                              \
         const long long t_ = __builtin_amdgcn_s_memtime();             \
-        pr[k] += t_ - tl; tl = t_;                                     \
+        ch_prof_add<W>(pr, k, t_ - tl, lane); tl = t_;                 \
     }
+// the profiled build's phase clocks pr: 16 waves keep a register pair per phase; 8 waves keep
+// phase k in lane ch_prof_lane(k) of one pair (their 88 tail terms take the registers: twelve
+// pairs spill).  Phase 9 is stamped inside the solve's two-lane branch (lanes 0 and CH_XL2 =
+// 3), so it lives in lane 3 and phase 3 in lane 9.
+constexpr int CH_NPROF = 12;
+__device__ __forceinline__ constexpr int ch_prof_lane(int k) { return k == 9 ? 3 : (k == 3 ? 9 : k); }
+template <int W>
+__device__ __forceinline__ void ch_prof_add(long long *pr, int k, long long d, int lane) {
+    if constexpr (W == 8) { if (lane == ch_prof_lane(k)) pr[0] += d; }
+    else pr[k] += d;
+}
 // fold row[8*c0 .. 8*c1) into acc in order: 4-term groups, four groups of reads in flight
 // (a group's 4 dependent adds, 32 clk, against an LDS read latency of ~70-100 clk).  The
 // reads run up to three groups past the end unconditionally (unused; LDS reads never fault):
@@ -856,6 +895,20 @@ __device__ __forceinline__ double ch_fold_span(double acc, const double *row, in
     return acc;
 }
 
+// register tail chunks C .. NC - 1 of the nc the row has left, in order (rt indexed statically:
+// the nested tests leave at the row's last chunk)
+template <int C, int NC>
+__device__ __forceinline__ double ch_tail(double acc, const double *rt, int nc) {
+    if constexpr (C < NC) {
+        if (nc > C) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) acc += rt[8 * C + k];
+            acc = ch_tail<C + 1, NC>(acc, rt, nc);
+        }
+    }
+    return acc;
+}
+
 // One fit of the chain, chain index x, its record staged in this wave's buffer B.  The fit's latest local source in chain order (marked CH_CRIT by
 // k_ex_relink) is the one its predecessor link hands over; everything else is done before it
 // arrives: the other sources' products (written to the staged record's term rows as they
@@ -865,7 +918,7 @@ __device__ __forceinline__ double ch_fold_span(double acc, const double *row, in
 // order, and the producer writes the value before the tag), its product is added in
 // registers -- never written to LDS -- and the terms after kc follow: the reference's order,
 // the same operations.
-template <bool PROF>
+template <bool PROF, int W>
 __device__ __forceinline__ bool ch_fit(int x, int lane, double *B, double2 *val, int *tag,
                                         int *cur, int &wm, double &o_out, long &c_out,
                                         long long *pr, long long &tl, double *gval,
@@ -875,7 +928,7 @@ __device__ __forceinline__ bool ch_fit(int x, int lane, double *B, double2 *val,
     long spins = 0;
     while (x - CH_R / 2 >= wm) {
         int m = 0x7fffffff;
-        for (int k = 0; k < CH_W; ++k)
+        for (int k = 0; k < W; ++k)
             m = min(m, __hip_atomic_load(&cur[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
         wm = m;
         if (x - CH_R / 2 >= wm) {
@@ -889,7 +942,8 @@ __device__ __forceinline__ bool ch_fit(int x, int lane, double *B, double2 *val,
     const int npad = __builtin_amdgcn_readfirstlane((int)(meta & 0xffffffff));
     const int nd = __builtin_amdgcn_readfirstlane((int)((meta >> 32) & 0x7fffffff));
     const bool pub = __builtin_amdgcn_readfirstlane((int)((unsigned long long)meta >> 63)) != 0;
-    if (npad > CH_TVS || nd > 64 || npad < 0 || nd < 0) return false;   // bug guard
+    if (npad > (W == 8 ? ch_nrt<PROF, W>() : CH_TVS) || nd > 64 || npad < 0 || nd < 0)
+        return false;   // bug guard
     const double *dyn = B + CH_HDR;
     double *tv = B + CH_HDR + 4 * nd;
     // wave-uniform solve constants, kept in SGPRs (scalar loads of the global record measured
@@ -980,35 +1034,48 @@ __device__ __forceinline__ bool ch_fit(int x, int lane, double *B, double2 *val,
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     if (fl) acc = ch_fold_span(acc, tv + frow * npad, 0, kmiss);
     CH_STAMP(3);
-    if (pend) {
-        long sp = 0;
-        __builtin_amdgcn_s_setprio(0);
-        for (;;) {
-            if (!done && __hip_atomic_load(&tag[slot], __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_WORKGROUP) == e.y) {
-                asm volatile("" ::: "memory");
-                const double2 v = val[slot];
-#pragma unroll
-                for (int s = 0; s < 6; ++s) tv[s * npad + e.x] = cf[s % 3] * (s < 3 ? v.x : v.y);
-                done = true;
-            }
-            if (__ballot(!done) == 0 || (RMT_CH_ABL & 4)) break;
-            if (++sp > CH_SPIN_LIMIT) return false;
-        }
-        __builtin_amdgcn_s_setprio(3);
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    }
-    if (fl) acc = ch_fold_span(acc, tv + frow * npad, kmiss, kc);
+    // the wait for the other sources, then the fold of the terms up to kc
+#define CH_WAIT_REST()                                                                   \
+    do {                                                                                 \
+        if (pend) {                                                                      \
+            long sp = 0;                                                                 \
+            __builtin_amdgcn_s_setprio(0);                                               \
+            for (;;) {                                                                   \
+                if (!done && __hip_atomic_load(&tag[slot], __ATOMIC_RELAXED,             \
+                                               __HIP_MEMORY_SCOPE_WORKGROUP) == e.y) {   \
+                    asm volatile("" ::: "memory");                                       \
+                    const double2 v = val[slot];                                         \
+                    _Pragma("unroll")                                                    \
+                    for (int s = 0; s < 6; ++s)                                          \
+                        tv[s * npad + e.x] = cf[s % 3] * (s < 3 ? v.x : v.y);            \
+                    done = true;                                                         \
+                }                                                                        \
+                if (__ballot(!done) == 0 || (RMT_CH_ABL & 4)) break;                     \
+                if (++sp > CH_SPIN_LIMIT) return false;                                  \
+            }                                                                            \
+            __builtin_amdgcn_s_setprio(3);                                               \
+            __builtin_amdgcn_wave_barrier();                                             \
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");                       \
+        }                                                                                \
+        if (fl) acc = ch_fold_span(acc, tv + frow * npad, kmiss, kc);                    \
+    } while (0)
+    // 8 waves: the other sources of a fit arrive only a link or two before its critical one
+    // (its row's fits x-2 .. x-4 before x-1), so what the fit still does after the last of
+    // them is on the chain's path as much as what it does after the critical value.  When no
+    // missing source's term lies after kc the tail rows are final already, and the register
+    // tail is read before that wait instead of after it.
+    bool early = false;
+    if constexpr (W == 8) early = cm && __ballot(!done && e.x > kc) == 0;
+    if (!early) CH_WAIT_REST();
     if (cm) {
-        // the terms after kc: their head chunk and the next two in registers before the
-        // critical value arrives (pure VALU adds after it), the rest from LDS.  Rows are padded
+        // the terms after kc: their head chunk and the next two (16 waves; ch_nrt: one in the
+        // profiled build, every chunk at 8 waves) in registers before the critical value
+        // arrives (pure VALU adds after it), the rest from LDS.  Rows are padded
         // with +0.0 to whole chunks (exact: a sum that starts at +0.0 is never -0.0).
         // (lanes 0-5 only: 64 lanes at a row stride would conflict on every LDS bank)
         const double *row = tv + frow * npad;
         const int h0 = (kc + 1) >> 3, hs = kc + 1 - 8 * h0, nch = npad >> 3;
-        // (the profiled build keeps one chunk: its counters need the registers)
-        constexpr int NRT = PROF ? 8 : 24;
+        constexpr int NRT = ch_nrt<PROF, W>();
         double rt[NRT];
         if (fl) {
             const double2 *r2 = (const double2 *)(row + 8 * h0);
@@ -1021,6 +1088,8 @@ __device__ __forceinline__ bool ch_fit(int x, int lane, double *B, double2 *val,
 #pragma unroll
             for (int k = 0; k < NRT; ++k) asm volatile("" : "+v"(rt[k]));
         }
+        if constexpr (W == 8)
+            if (early) CH_WAIT_REST();
         double2 vc;
         long sp = 0;
         // the tag and the value read back to back in one LDS round trip (relaxed atomic
@@ -1041,7 +1110,7 @@ __device__ __forceinline__ bool ch_fit(int x, int lane, double *B, double2 *val,
         }
         if constexpr (PROF) {
             if (sp) tr_crit = eyc;
-            pr[7] += sp;
+            ch_prof_add<W>(pr, 7, sp, lane);
             CH_STAMP(2);
             tr_ready = __builtin_amdgcn_s_memrealtime();
         }
@@ -1054,6 +1123,10 @@ __device__ __forceinline__ bool ch_fit(int x, int lane, double *B, double2 *val,
 #pragma unroll
                 for (int k = 0; k < 8; ++k)
                     if (k >= hs) acc += rt[k];
+                if constexpr (W == 8) {   // the whole tail: adds only, no LDS after the arrival
+                    acc = ch_tail<1, NRT / 8>(acc, rt, nch - h0);
+                    break;
+                }
                 if constexpr (NRT > 8) {
                     if (h0 + 1 >= nch) break;
                     acc += rt[8]; acc += rt[9]; acc += rt[10]; acc += rt[11];
@@ -1110,18 +1183,20 @@ __device__ __forceinline__ bool ch_fit(int x, int lane, double *B, double2 *val,
     return true;
 }
 
-template <bool PROF>
-__global__ void __launch_bounds__(CH_W * 64) k_ex_chain(ChainArgs C, long long *gprof) {
+// W waves per part (8 or 16: rmt_opts::ch_waves, the W the prep's k_ex_runs dealt the fits to)
+template <bool PROF, int W>
+__global__ void __launch_bounds__(W * 64) k_ex_chain(ChainArgs C, long long *gprof) {
+    static_assert(W == 8 || W == CH_W, "k_ex_runs' table has CH_W entries per part");
     __shared__ double2 val[CH_R];
     __shared__ int tag[CH_R];
-    __shared__ __attribute__((aligned(16))) double buf[CH_W][CH_BUFD];
-    __shared__ int cur[CH_W];
+    __shared__ __attribute__((aligned(16))) double buf[W][ch_bufd<W>()];
+    __shared__ int cur[W];
     const int *ctl = C.ws.ctl;
     const char *arena = C.ws.arena;
     double *X1e = C.X1e, *X2e = C.X2e;
     for (int s = threadIdx.x; s < CH_R; s += blockDim.x) tag[s] = -1;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (threadIdx.x < CH_W) cur[threadIdx.x] = 0;
+    if (threadIdx.x < W) cur[threadIdx.x] = 0;
     __syncthreads();
     if (ctl[EXC_FALLBACK] || ctl[EXC_ABORT]) return;
     // this workgroup runs part blockIdx.x; x below is the ordinal within the part
@@ -1138,7 +1213,7 @@ __global__ void __launch_bounds__(CH_W * 64) k_ex_chain(ChainArgs C, long long *
     if (x < total) CH_LOAD(r);
     int wm = 0;
     bool ok = true;
-    long long pr[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tl = 0;
+    long long pr[W == 8 ? 1 : CH_NPROF] = {}, tl = 0;
     if constexpr (PROF) tl = __builtin_amdgcn_s_memtime();
     double o = 0.0;      // previous fit's value (lane 0: X1, lane 3: X2) and cell
     long c = -1;
@@ -1158,14 +1233,18 @@ __global__ void __launch_bounds__(CH_W * 64) k_ex_chain(ChainArgs C, long long *
         if (x2 <= x) { ok = false; break; }   // bug guard: the wave's sequence must advance
         if (x2 < total) CH_LOAD(r2);
         CH_STAMP(6);
-        const bool fit_ok = ch_fit<PROF>(x, lane, B, val, tag, cur, wm, o, c, pr, tl,
+        const bool fit_ok = ch_fit<PROF, W>(x, lane, B, val, tag, cur, wm, o, c, pr, tl,
                                          C.ws.gval, base + x, C.trace, base);
         if (!fit_ok) { ok = false; break; }
         x = x2; r = r2;
     }
-    if constexpr (PROF)
-        if (lane == 0)
+    if constexpr (PROF) {
+        if constexpr (W == 8) {
+            if (lane < CH_NPROF) atomicAdd((unsigned long long *)&gprof[ch_prof_lane(lane)], pr[0]);
+        } else if (lane == 0) {
             for (int k = 0; k < 12; ++k) atomicAdd((unsigned long long *)&gprof[k], pr[k]);
+        }
+    }
     if (ok && c >= 0 && (lane == 0 || lane == CH_XL2)) (lane == 0 ? X1e : X2e)[c] = o;
     __hip_atomic_store(&cur[wv], 0x7fffffff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (!ok && lane == 0) {   // the abort word names this part and the waiting fit (extrap.hpp)
@@ -1181,6 +1260,9 @@ static int chain_parts(const rmt_ctx *ctx, int ML, int *ncol, int *nlg) {
     *nlg = std::max(1, std::min({g, ML, CH_MAXP / *ncol}));
     return *ncol * *nlg;
 }
+
+// waves per part (rmt_opts::ch_waves; set_option and the environment admit 8 and 16 only)
+static int chain_waves(const rmt_ctx *ctx) { return ctx->opt.ch_waves == 8 ? 8 : CH_W; }
 
 bool extrap_chain_supported(int ny, int nx, int ML) {
     return ML >= 1 && ML <= EX_MAXL && ny >= 3 && nx >= 3;
@@ -1209,7 +1291,7 @@ int extrap_chain_prep(rmt_ctx *ctx, const ExWs &ws, const double *X1o, const dou
     int ncol, nlg;
     const int nparts = chain_parts(ctx, ML, &ncol, &nlg);
     k_ex_order<<<1, 1024, 0, st>>>(ws, ny, ML);
-    k_ex_split<<<1, 1024, 0, st>>>(ws, nx, ML, ncol, nlg);
+    k_ex_split<<<1, 1024, 0, st>>>(ws, nx, ML, ncol, nlg, chain_waves(ctx));
     const unsigned idb = grid1d(ws.maxt, 256);
     k_ex_chainidx<<<idb, 256, 0, st>>>(ws, ny, nx, ML, ws.status);
     k_ex_local<<<1, 1024, 0, st>>>(ws, ML);
@@ -1260,8 +1342,10 @@ int extrap_chain_run(rmt_ctx *ctx, const ExWs &ws, const double *X1o, const doub
     if (call.chain_event && !call.event_with_values)
         RMT_HIP(hipEventRecord(call.chain_event, st));
     ChainArgs C{ws, (double *)X1o, (double *)X2o, ML, ws.status, nullptr};
+    const int nw = chain_waves(ctx);
     if (!ctx->opt.ex_profile) {
-        k_ex_chain<false><<<nparts, CH_W * 64, 0, st>>>(C, nullptr);
+        if (nw == 8) k_ex_chain<false, 8><<<nparts, 8 * 64, 0, st>>>(C, nullptr);
+        else k_ex_chain<false, CH_W><<<nparts, CH_W * 64, 0, st>>>(C, nullptr);
         RMT_LAUNCHED();
     } else {
         // diagnostic: per-phase shader clocks summed over the chain waves
@@ -1281,7 +1365,8 @@ int extrap_chain_run(rmt_ctx *ctx, const ExWs &ws, const double *X1o, const doub
             C.trace = dtr;
         }
         RMT_HIP(hipEventRecord(e0, st));
-        k_ex_chain<true><<<nparts, CH_W * 64, 0, st>>>(C, gp);
+        if (nw == 8) k_ex_chain<true, 8><<<nparts, 8 * 64, 0, st>>>(C, gp);
+        else k_ex_chain<true, CH_W><<<nparts, CH_W * 64, 0, st>>>(C, gp);
         RMT_LAUNCHED();
         RMT_HIP(hipEventRecord(e1, st));
         RMT_HIP(hipMemcpyAsync(hp, gp, sizeof(hp), hipMemcpyDeviceToHost, st));

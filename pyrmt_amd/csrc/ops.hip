@@ -36,6 +36,7 @@ static const struct { const char *name, *env; int rmt_opts::*f; } kOpts[] = {
     {"test_nowait_drop", "RMT_TEST_NOWAIT_DROP", &rmt_opts::test_nowait_drop},
     {"chain_cols", "RMT_CH_PARTS", &rmt_opts::ch_cols},
     {"chain_layer_groups", "RMT_CH_LAYERS", &rmt_opts::ch_lgroups},
+    {"chain_waves", "RMT_CH_WAVES", &rmt_opts::ch_waves},
     {"edge_slots", "RMT_EDGE_SLOTS_USED", &rmt_opts::edge_slots},
     {"edge_stream", "RMT_EDGE_STREAM", &rmt_opts::edge_stream},
     {"sl_phi", "RMT_SL_PHI", &rmt_opts::sl_phi},
@@ -62,6 +63,7 @@ static rmt_opts opts_from_env() {
     o.test_delay_side = std::max(0, o.test_delay_side);
     o.test_delay_main = std::max(0, o.test_delay_main);
     o.test_delay_geo = std::max(0, o.test_delay_geo);
+    if (o.ch_waves != 8 && o.ch_waves != 16) o.ch_waves = rmt_opts().ch_waves;
     return o;
 }
 
@@ -827,6 +829,8 @@ int rmt_ctx_set_option(rmt_ctx *ctx, const char *name, int value) {
     RMT_CHECK(ctx && name, RMT_EINVAL, "null argument");
     for (const auto &k : kOpts)
         if (!strcmp(k.name, name)) {
+            RMT_CHECK(k.f != &rmt_opts::ch_waves || value == 8 || value == 16, RMT_EINVAL,
+                      "chain_waves is 8 or 16");
             ctx->opt.*(k.f) = value;
             ctx->bytes_gen++;   // a carried step state was prepared under the old options
             return RMT_OK;

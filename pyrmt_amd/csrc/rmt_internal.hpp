@@ -102,6 +102,8 @@ struct rmt_opts {
                               // (the pre-fix behaviour, to show the hazard the wait removes)
     int ch_cols = 2;          // RMT_CH_PARTS: chain workgroups per layer group (column ranges)
     int ch_lgroups = 0;       // RMT_CH_LAYERS: chain layer groups (0: one per layer)
+    int ch_waves = 8;         // RMT_CH_WAVES: waves per chain workgroup, 8 or 16 (8: the whole
+                              // register tail, extrap_chain.hip ch_nrt)
     int edge_slots = 64;      // RMT_EDGE_SLOTS_USED: edge-tile lists kept (1..64; fewer evict)
     int edge_stream = 1;      // RMT_EDGE_STREAM: a full stage's edge tiles beside its interior
     int sl_phi = 1;           // RMT_SL_PHI: the side stream's SL pass also writes phi + fluid bits

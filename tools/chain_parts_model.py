@@ -91,6 +91,20 @@ side = [int((f[2] - cmin) * 2 // span) for f in fits]
 col2 = side
 layer = [f[0] for f in fits]
 side_layer = [s * ML + L for s, L in zip(side, layer)]
+# dependency levels (a fit's level = 1 + the deepest of its sources) and, per part of the
+# 6-part split, how many of its fits share a level: what a part's waves can run side by side
+level = np.zeros(nf, dtype=np.int64)
+for t in order:
+    level[t] = 1 + max((level[s] for s, _ in deps[t]), default=0)
+depth = int(level.max())
+print(f"DAG depth {depth} levels; {nf / depth:.2f} fits per level over the whole chain")
+for name, po in (("2 column parts", col2), ("side x layer (6)", side_layer)):
+    po_a = np.array(po)
+    for p in range(po_a.max() + 1):
+        lv = level[po_a == p]
+        print(f"{name:22s} part {p}: {len(lv)} fits on {len(np.unique(lv))} levels, "
+              f"{len(lv) / len(np.unique(lv)):.2f} fits per occupied level, "
+              f"{len(lv) / depth:.2f} per level of the chain")
 side_l01 = [s * 2 + min(L, 1) for s, L in zip(side, layer)]
 for name, po in (("2 column parts", col2), ("side x layer (6)", side_layer),
                  ("side x {0},{1,2} (4)", side_l01)):
