@@ -65,7 +65,7 @@ int rmt_version(void);
  * or a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream).  ny, nx >= 2; the
  * collocated operators (5-point-wide stencils) are only defined on ny, nx >= 5 -- a smaller
  * context serves only the DCT-II Neumann solve (rmt_mac_solve_poisson_neumann,
- * rmt_selftest_dct2_rows) and, square from 3 x 3, the periodic FFT solve. */
+ * rmt_selftest_dct2_rows) and, from 3 x 3, the periodic FFT solve. */
 int rmt_ctx_create(int ny, int nx, int device, void *stream, rmt_ctx **out);
 int rmt_ctx_set_stream(rmt_ctx *ctx, void *stream);
 int rmt_ctx_destroy(rmt_ctx *ctx);
@@ -390,8 +390,9 @@ int rmt_sim_phase_times(rmt_sim *sim, double *ms8, long *calls8);
 int rmt_sim_diagnostics(rmt_sim *sim, rmt_diag *out, int max_records, int *n_records);
 
 /* ---- periodic branch (functions.py:1177-1290; tests/test_poisson.py:24-78) -----------
- * Overlap grid (x[-1] == x[0]): operators on the reduced (N-1)^2 sub-grid, tiled back.
- * lamx / lamy: HOST per-axis symbols -(sin(2 pi k / m) / h)^2, length m = N - 1. */
+ * Overlap grid (x[-1] == x[0]): operators on the reduced (ny-1) x (nx-1) sub-grid, tiled
+ * back; ny, nx >= 3, rectangular grids allowed.
+ * lamx / lamy: HOST per-axis symbols -(sin(2 pi k / m) / h)^2, length m = nx - 1 / ny - 1. */
 int rmt_divergence_periodic(rmt_ctx *ctx, const double *a, const double *b, double dx, double dy,
                             double *divU);                           /* functions.py:1236 */
 int rmt_pressure_gradient_periodic(rmt_ctx *ctx, const double *p, double dx, double dy,

@@ -5,6 +5,8 @@ Bars (stated per test):
   * bit-exact for kernels with no transcendental function and no FFT (FD helpers,
     upwind, bilinear, SL-RK4, solid stress, Rhie-Chow divergence, pressure gradient,
     WENO5, pure-fluid momentum, BCs);
+  * a momentum step with a solid is bit-exact too on a level set whose H is exact (phi in
+    {-1, 0, +1}: H = {0, 0.5, 1}, no sin): tests/test_gpu_offsquare.py, off the square;
   * kernels using sin (smoothed Heaviside) / exp (extrapolation weights) / the DCT-I:
     tolerance stated in the test (device libm and rocFFT differ from glibc/pocketfft in
     the last bits);
