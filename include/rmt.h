@@ -648,6 +648,33 @@ int rmt_mac_per_steps_sl(rmt_ctx *ctx, double *u, double *v, double nu, double d
                          const double *ly, double cfl_switch, int nsteps, double *p,
                          int *sl_steps);
 
+/* ---- reference-map reinitialisation with stored deformation (mac_reinit.hip):
+ * benchmarks/mac_reinit_test.py:23-113 (Rycroft 2018) ----
+ * All planes (ny, nx) of the context unless stated; arrays of plane pointers (q, out, Fs, Ftot)
+ * are host arrays of device pointers.  Bit-exact against the reference but for H's sine. */
+/* functions.py:194-227 for np (1..8) planes on one RK4 backtrace: out[k] = the bits of
+ * rmt_advect_sl_rk4(q[k]) and, phi non-NULL, of rmt_mask_solid on top (q * 0.0 keeps -0.0 and
+ * NaN).  No out[k] may be one of the q planes. */
+int rmt_advect_sl_rk4_multi(rmt_ctx *ctx, int np, const double *const *q, const double *a,
+                            const double *b, const double *X, const double *Y, double dt,
+                            double dx, double dy, const double *phi, double *const *out);
+/* :23-33, :74-81: F_current from the map (grad_central_*_2nd, |detG| < 1e-9 -> 1e-9),
+ * J_ep = 1 / detG, Ftot = F_current . Fs (components 11, 12, 21, 22),
+ * S = (1 - smoothed_heaviside(phi, w_t)) * mu_s * b.  Ftot: NULL, or four planes. */
+int rmt_mac_total_stress(rmt_ctx *ctx, const double *X1, const double *X2,
+                         const double *const *Fs, const double *phi, double dx, double dy,
+                         double w_t, double mu_s, double *Sxx, double *Sxy, double *Syy,
+                         double *J_ep, double *const *Ftot);
+/* :74-85 in one launch: that stress, its central divergence averaged to the interior faces,
+ * wall faces 0: fu (ny, nx+1), fv (ny+1, nx), J_ep.  The same bits as rmt_mac_total_stress,
+ * rmt_grad_x_2nd / rmt_grad_y_2nd and the face average composed; S stays in LDS. */
+int rmt_mac_total_force(rmt_ctx *ctx, const double *X1, const double *X2,
+                        const double *const *Fs, const double *phi, double dx, double dy,
+                        double w_t, double mu_s, double *fu, double *fv, double *J_ep);
+/* :91-94: out3 (device, 3 doubles) = max J_ep, min J_ep (NaN propagates) and the number of
+ * cells over phi <= 0 (-inf, +inf, 0 when there is none). */
+int rmt_mac_epoch_distortion(rmt_ctx *ctx, const double *J_ep, const double *phi, double *out3);
+
 /* The MAC step decomposed into row slabs (config 5 on several GPUs).
  * No reference interface: pyRMT runs mac_multi_disc_lid.py:62-98 in one process.  Slab
  * `rank` of G owns cell rows [row_splits[rank], row_splits[rank+1]) (even, > RMT_SLAB_HALO

@@ -221,6 +221,11 @@ SIGNATURES = {
                                            _P, ctypes.POINTER(_I)]),
     "rmt_mac_per_steps_sl": (_I, [_P, _P, _P, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _P, _P,
                                   _D, _I, _P, ctypes.POINTER(_I)]),
+    # reference-map reinitialisation (mac.py MacReinitDisc, mac_reinit.hip)
+    "rmt_advect_sl_rk4_multi": (_I, [_P, _I, _P, _P, _P, _P, _P, _D, _D, _D, _P, _P]),
+    "rmt_mac_total_stress": (_I, [_P, _P, _P, _P, _P, _D, _D, _D, _D, _P, _P, _P, _P, _P]),
+    "rmt_mac_total_force": (_I, [_P, _P, _P, _P, _P, _D, _D, _D, _D, _P, _P, _P]),
+    "rmt_mac_epoch_distortion": (_I, [_P, _P, _P, _P]),
 }
 
 _lib = None

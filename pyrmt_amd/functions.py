@@ -318,6 +318,43 @@ def advect_reference_map(q, a, b, X, Y, dt, dx, dy, phi, scheme='semilagrangian'
                      "'central2', 'weno5' or 'conservative')" % (scheme,))
 
 
+def _plane_ptrs(ts):
+    """A host array of the device pointers of planes (librmt's `const double *const *`)."""
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _advect_sl_rk4_multi(c, qs, a, b, X, Y, dt, dx, dy, phi, outs):
+    """rmt_advect_sl_rk4_multi on device tensors (no checks, no allocation)."""
+    L.check(L.lib().rmt_advect_sl_rk4_multi(c.bind(), len(qs), _plane_ptrs(qs), _p(a), _p(b),
+                                            _p(X), _p(Y), float(dt), float(dx), float(dy),
+                                            _p(phi), _plane_ptrs(outs)),
+            "advect_reference_maps")
+
+
+def advect_reference_maps(qs, a, b, X, Y, dt, dx, dy, phi=None):
+    """No reference counterpart: advect_reference_map(q, ..., 'semilagrangian') for 1..8 planes
+    qs that share one velocity, on one RK4 backtrace (benchmarks/mac_reinit_test.py:65-68 runs
+    it once a plane).  phi given: each result times the solid mask (phi <= 0), the driver's
+    `* m`, in the same pass.  The non-finite-velocity guard runs once for the group.  Returns
+    the list of advected planes, each the bits of the single-plane operators."""
+    qs = list(qs)
+    if not 1 <= len(qs) <= 8:
+        raise ValueError("advect_reference_maps: 1..8 planes")
+    io = _IO(a, b, X, Y, phi, *qs)
+    ad, bd, Xd, Yd, pd = map(io.dev, (a, b, X, Y, phi))
+    qd = [io.dev(q) for q in qs]
+    if any(tuple(t.shape) != tuple(ad.shape) for t in qd + [bd, Xd, Yd] + ([pd] if pd is not None else [])):
+        raise ValueError("advect_reference_maps: planes of one (Ny, Nx) shape")
+    c = ctx_for(*ad.shape)
+    fin = ctypes.c_int(0)
+    L.check(L.lib().rmt_all_finite2(c.bind(), _p(ad), _p(bd), ctypes.byref(fin)))
+    if not fin.value:
+        raise FloatingPointError("advect_reference_map: non-finite velocity (the simulation diverged)")
+    outs = [io.empty(ad.shape) for _ in qd]
+    _advect_sl_rk4_multi(c, qd, ad, bd, Xd, Yd, dt, dx, dy, pd, outs)
+    return [io.out(o) for o in outs]
+
+
 def rebuild_phi_from_reference_map(X1, X2, phi_init_func):
     """functions.py:1366-1367 for a disc level set (the drivers' lambda or bc.Disc)."""
     d = resolve_shape(phi_init_func)

@@ -14,6 +14,9 @@ The free-slip box (mac.py:179-193, 656-689): ``momentum_predictor_freeslip``,
 ``MacMultiDisc(walls="freeslip")``: ``MacDiscTaylorGreen`` / ``disc_in_tg_run_one``
 (benchmarks/mac_disc_in_tg_convergence.py) and ``MacTwoDiscContact``
 (benchmarks/mac_two_disc_contact.py).
+Reference-map reinitialisation with stored deformation (benchmarks/mac_reinit_test.py,
+mac_reinit.hip): ``total_stress``, ``total_force``, ``epoch_distortion`` and the loop
+``MacReinitDisc`` / ``mac_reinit_run``, composed from operators on device tensors.
 """
 import ctypes
 import math
@@ -21,7 +24,7 @@ import math
 import numpy as np
 
 from . import _lib as L
-from .functions import _IO, _p, ctx_for, extrapolate_reference_map
+from .functions import _IO, _p, _plane_ptrs, ctx_for, extrapolate_reference_map
 from .simulation import _wrap_device
 
 
@@ -943,3 +946,207 @@ class MacTwoDiscContact(MacMultiDisc):
         d = self.diagnostics()
         cx = d["cx"].reshape(-1, 2)
         return np.column_stack([d["t"], cx[:, 0], cx[:, 1], cx[:, 1] - cx[:, 0]])
+
+
+# ------------------------------------------------------------------ reinitialisation --
+# benchmarks/mac_reinit_test.py:23-113 (Rycroft 2018) through mac_reinit.hip: the reference map
+# is reset to the identity when the epoch's distortion gets large, the deformation gathered so
+# far lives on as four advected, extrapolated planes Fs, the shape as a stored level set phiref,
+# and the stress comes from F_total = F_current . Fs.
+def _planes4(io, Fs, shape, what):
+    Fd = [io.dev(p) for p in Fs]
+    if len(Fd) != 4 or any(tuple(p.shape) != tuple(shape) for p in Fd):
+        raise ValueError(f"{what}: Fs is four planes (11, 12, 21, 22) of the map's shape")
+    return Fd
+
+
+def total_stress(X1, X2, Fs, phi, dx, dy, w_t, mu_s, with_Ftot=False):
+    """mac_reinit_test.py:74-81: (Sxx, Sxy, Syy, J_ep) of the total deformation
+    F_current(X1, X2) . Fs, S = (1 - smoothed_heaviside(phi, w_t)) mu_s b; with_Ftot: a fifth
+    item, the list of the four Ftot planes (what a reinitialisation stores, :98)."""
+    shape = _plane2("total_stress", X1=X1, X2=X2, phi=phi)
+    io = _IO(X1, X2, phi, *Fs); X1d, X2d, pd = map(io.dev, (X1, X2, phi))
+    Fd = _planes4(io, Fs, shape, "total_stress")
+    outs = [io.empty(shape) for _ in range(4)]
+    Ft = [io.empty(shape) for _ in range(4)] if with_Ftot else None
+    L.check(L.lib().rmt_mac_total_stress(ctx_for(*shape).bind(), _p(X1d), _p(X2d), _plane_ptrs(Fd),
+                                         _p(pd), float(dx), float(dy), float(w_t), float(mu_s),
+                                         *map(_p, outs), _plane_ptrs(Ft) if Ft else None),
+            "total_stress")
+    res = tuple(io.out(o) for o in outs)
+    return res + ([io.out(p) for p in Ft],) if with_Ftot else res
+
+
+def total_force(X1, X2, Fs, phi, dx, dy, w_t, mu_s):
+    """mac_reinit_test.py:74-85 in one launch: (fu (Ny, Nx+1), fv (Ny+1, Nx), J_ep), the face
+    forces of that stress (central divergence, averaged to the interior faces, wall faces 0);
+    the same bits as total_stress, grad_central_*_2nd and the average composed."""
+    shape = _plane2("total_force", X1=X1, X2=X2, phi=phi)
+    io = _IO(X1, X2, phi, *Fs); X1d, X2d, pd = map(io.dev, (X1, X2, phi))
+    Fd = _planes4(io, Fs, shape, "total_force")
+    ny, nx = shape
+    fu = io.empty((ny, nx + 1)); fv = io.empty((ny + 1, nx)); J = io.empty(shape)
+    L.check(L.lib().rmt_mac_total_force(ctx_for(ny, nx).bind(), _p(X1d), _p(X2d), _plane_ptrs(Fd),
+                                        _p(pd), float(dx), float(dy), float(w_t), float(mu_s),
+                                        _p(fu), _p(fv), _p(J)), "total_force")
+    return io.out(fu), io.out(fv), io.out(J)
+
+
+def epoch_distortion(J_ep, phi, out=None):
+    """mac_reinit_test.py:91-94: (max J_ep, min J_ep, number of cells) over phi <= 0 as three
+    doubles (a device tensor for device inputs, written into `out` when given; -inf, +inf, 0
+    without a solid cell; NaN propagates as in ndarray.max)."""
+    shape = _plane2("epoch_distortion", J_ep=J_ep, phi=phi)
+    io = _IO(J_ep, phi); Jd, pd = io.dev(J_ep), io.dev(phi)
+    o = io.empty((3,)) if out is None else out
+    L.check(L.lib().rmt_mac_epoch_distortion(ctx_for(*shape).bind(), _p(Jd), _p(pd), _p(o)),
+            "epoch_distortion")
+    return io.out(o)
+
+
+class MacReinitDisc:
+    """The loop body of benchmarks/mac_reinit_test.py:59-106 on device tensors, composed from
+    operators (no fused step): a soft disc (R 0.2 at (0.6, 0.5)) in the lid cavity whose map
+    is reinitialised when the epoch distortion max(max J, 1 / min J) over the solid exceeds
+    reinit_J.  A step: phi = phiref(xi) (bilinear), the six planes xi1, xi2, Fs advected on one
+    backtrace and masked (rmt_advect_sl_rk4_multi), three extrapolations, phi again, the face
+    forces of the total stress in one launch (rmt_mac_total_force), predictor, projection, the
+    distortion reduction; the host reads four scalars (max J, min J, the solid's cell count,
+    max|u|) once and decides the reinitialisation and the `diverged` stop as :91-106 do.
+    reinit=False: the plain loop, which folds and stops.  The advection skips the per-plane
+    non-finite-velocity guard: the loop stops on a non-finite u before the next step reads it.
+
+    `record`: one (t, dist, min J_ep, max J_ep, n_reinit, max|u|) per step."""
+
+    X0, Y0, R = 0.6, 0.5, 0.2
+    STATE = ("u", "v", "X1", "X2", "Fs", "phiref", "t", "n_reinit")
+
+    def __init__(self, N=96, reinit=True, U_lid=1.0, mu_s=0.3, mu_f=0.01, rho=1.0, reinit_J=1.8):
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("pyrmt_amd needs a visible MI355X")
+        self.torch, self.N, self.reinit, self.reinit_J = torch, int(N), bool(reinit), reinit_J
+        self.U_lid, self.mu_s, self.mu_f, self.rho = U_lid, mu_s, mu_f, rho
+        dx, dy = mac_grid(N, N)
+        self.dx, self.dy, self.w_t, self.nu = dx, dy, 2.0 * dx, mu_f / rho
+        xc = (np.arange(N) + 0.5) * dx
+        Xc, Yc = np.meshgrid(xc, xc)
+        Xg, Yg = np.meshgrid(np.arange(N) * dx, np.arange(N) * dy)
+        phi = np.sqrt((Xc - self.X0)**2 + (Yc - self.Y0)**2) - self.R          # :42-47
+        m = (phi <= 0).astype(float)
+        X1, X2 = extrapolate_reference_map(Xc * m, Yc * m, phi, dx, dy, 3)
+        dev = lambda h: torch.from_numpy(np.ascontiguousarray(h, dtype=np.float64)).cuda()
+        self.Xc, self.Yc, self.Xg, self.Yg = map(dev, (Xc, Yc, Xg, Yg))
+        self.X1, self.X2, self.phiref = dev(X1), dev(X2), dev(phi)
+        one, zero = np.ones((N, N)), np.zeros((N, N))
+        self.Fs = [dev(one), dev(zero), dev(zero), dev(one)]
+        self.u, self.v = dev(np.zeros((N, N + 1))), dev(np.zeros((N + 1, N)))
+        self.lx, self.ly = _axis_eigs(poisson_eigs_neumann(N, N, dx, dy))
+        cs = np.sqrt(mu_s / rho)
+        self.dt = float(min(0.3 * dx / U_lid, 0.2 * dx * dx / self.nu, 0.3 * dx / (cs + 1e-9)))
+        self.ctx = ctx_for(N, N)
+        self.stats = torch.empty(4, dtype=torch.float64, device="cuda")
+        self.t, self.nsteps, self.n_reinit, self.diverged, self.record = 0.0, 0, 0, False, []
+        self.phi = self.J_ep = None
+        self.reinit_steps = []
+
+    def _geom(self):
+        """:55-56: phi = phiref(xi), bilinear at the cell-centred offset."""
+        from .functions import bilinear_interpolate
+        N = self.N
+        return bilinear_interpolate(self.phiref, self.X1 - 0.5 * self.dx, self.X2 - 0.5 * self.dy,
+                                    self.dx, self.dy, N, N)
+
+    def _extrapolate_pairs(self, phi):
+        dx, dy, Fs = self.dx, self.dy, self.Fs
+        Fs[0], Fs[1] = extrapolate_reference_map(Fs[0], Fs[1], phi, dx, dy, 3)
+        Fs[2], Fs[3] = extrapolate_reference_map(Fs[2], Fs[3], phi, dx, dy, 3)
+
+    def step(self, nsteps=1, t_end=math.inf):
+        from .functions import _advect_sl_rk4_multi
+        torch, dx, dy, dt = self.torch, self.dx, self.dy, self.dt
+        for _ in range(int(nsteps)):
+            if self.diverged or not self.t < t_end:
+                break
+            if self.t + dt > t_end:
+                dt = t_end - self.t                                            # :61-62
+            u, v = self.u, self.v
+            u_c = 0.5 * (u[:, :-1] + u[:, 1:]); v_c = 0.5 * (v[:-1, :] + v[1:, :])
+            phi = self._geom()
+            qs = [self.X1, self.X2] + self.Fs
+            outs = [torch.empty_like(q) for q in qs]
+            _advect_sl_rk4_multi(self.ctx, qs, u_c.contiguous(), v_c.contiguous(), self.Xg, self.Yg,
+                                 dt, dx, dy, phi, outs)
+            self.X1, self.X2 = extrapolate_reference_map(outs[0], outs[1], phi, dx, dy, 3)
+            self.Fs = outs[2:]
+            self._extrapolate_pairs(phi)
+            phi = self._geom()
+            fu, fv, J_ep = total_force(self.X1, self.X2, self.Fs, phi, dx, dy, self.w_t, self.mu_s)
+            ustar, vstar = momentum_predictor(u, v, self.nu, dx, dy, dt, self.U_lid, fu=fu, fv=fv,
+                                              rho=self.rho)
+            # project(), the symbol's axes split once at set-up (not per step)
+            un, vn, p = torch.empty_like(u), torch.empty_like(v), torch.empty_like(phi)
+            L.check(L.lib().rmt_mac_project(self.ctx.bind(), _p(ustar), _p(vstar), dx, dy, dt,
+                                            float(self.rho), _hp(self.lx), _hp(self.ly), _p(un),
+                                            _p(vn), _p(p)), "project")
+            self.u, self.v = un, vn
+            self.t += dt
+            self.nsteps += 1
+            epoch_distortion(J_ep, phi, out=self.stats[:3])
+            self.stats[3] = self.u.abs().max()
+            maxJ, minJ, count, umax = self.stats.tolist()        # the step's one host read
+            solid = count > 0
+            dist = max(maxJ, 1.0 / max(minJ, 1e-6)) if solid else math.inf     # :91-96
+            if self.reinit and dist > self.reinit_J and solid:                 # :97-103
+                # Fs <- Ftot: the stress kernel once more with Ftot requested, so that the
+                # per-step path never writes those four planes
+                self.Fs = list(total_stress(self.X1, self.X2, self.Fs, phi, dx, dy, self.w_t,
+                                            self.mu_s, with_Ftot=True)[4])
+                self._extrapolate_pairs(phi)
+                self.phiref = phi
+                self.X1, self.X2 = self.Xc.clone(), self.Yc.clone()
+                self.n_reinit += 1
+                self.reinit_steps.append(self.nsteps)
+            self.phi, self.J_ep = phi, J_ep
+            self.record.append((self.t, dist, minJ, maxJ, self.n_reinit, umax))
+            if not math.isfinite(umax) or not solid:                           # :105-106
+                self.diverged = True
+        return self
+
+    def state(self):
+        """Host copies of u, v, X1, X2, Fs (4, N, N), phiref, and t, n_reinit."""
+        g = lambda t: t.cpu().numpy()
+        return dict(u=g(self.u), v=g(self.v), X1=g(self.X1), X2=g(self.X2),
+                    Fs=np.stack([g(p) for p in self.Fs]), phiref=g(self.phiref), t=self.t,
+                    n_reinit=self.n_reinit)
+
+    def set_state(self, state):
+        """The fields of state() (arrays or device tensors; any subset)."""
+        unknown = set(state) - set(self.STATE)
+        if unknown:
+            raise KeyError(f"set_state: unknown fields {sorted(unknown)}; one of {self.STATE}")
+        N, io = self.N, _IO(None)
+        shapes = {"u": (N, N + 1), "v": (N + 1, N), "Fs": (4, N, N)}
+        for k, val in state.items():
+            if k in ("t", "n_reinit"):
+                setattr(self, k, float(val) if k == "t" else int(val))
+                continue
+            if tuple(np.shape(val)) != shapes.get(k, (N, N)):
+                raise ValueError(f"set_state: {k} has shape {tuple(np.shape(val))}")
+            d = io.dev(val).clone()
+            setattr(self, k, [d[i].contiguous() for i in range(4)] if k == "Fs" else d)
+        self.diverged = False
+
+    def get(self, name):
+        return getattr(self, name).cpu().numpy()
+
+
+def mac_reinit_run(N=96, t_end=15.0, reinit=True, U_lid=1.0, mu_s=0.3, mu_f=0.01, rho=1.0,
+                   reinit_J=1.8, return_sim=False):
+    """mac_reinit_test.py:36-113 (run): integrate to t_end or to the `diverged` stop; returns
+    the time reached (return_sim: (t, the MacReinitDisc))."""
+    if not math.isfinite(t_end):
+        raise ValueError("mac_reinit_run: a finite t_end")
+    sim = MacReinitDisc(N, reinit, U_lid, mu_s, mu_f, rho, reinit_J)
+    sim.step(2**31 - 1, t_end)
+    return (sim.t, sim) if return_sim else sim.t
