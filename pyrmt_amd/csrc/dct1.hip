@@ -214,10 +214,7 @@ __device__ __forceinline__ void put_row_sum(const double (&xa)[PP], const double
             red[tid] = acc;
         }
         __syncthreads();
-        for (int w = 128; w > 0; w >>= 1) {
-            if (tid < w) red[tid] = red[tid] + red[tid + w];
-            __syncthreads();
-        }
+        tree_fold<256>(red, fold_add(), tid);
         if (tid == 0) rs[r] = red[0];
     }
 }

@@ -562,10 +562,10 @@ __global__ void __launch_bounds__(1024) k_ex_split(ExWs ws, int nx, int ML, int 
     }
     smin[t] = mn; smax[t] = mx;
     __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if (t < w) { smin[t] = min(smin[t], smin[t + w]); smax[t] = max(smax[t], smax[t + w]); }
-        __syncthreads();
-    }
+    tree_fold<1024>([&](int t, int u) {
+        smin[t] = min(smin[t], smin[u]);
+        smax[t] = max(smax[t], smax[u]);
+    });
     if (t == 0) {
         ws.ctl[EXC_CMIN] = smin[0];
         ws.ctl[EXC_CMAX] = smax[0] >= smin[0] ? smax[0] - smin[0] + 1 : 1;   // span

@@ -10,19 +10,18 @@
 //
 // Interior layouts: u-faces (ny, nx - 1) (face i = m + 1 of row j), v-faces (ny - 1, nx)
 // (face row j = r + 1).  The per-face arithmetic follows the reference's NumPy expressions
-// operand for operand (bit-exact operators); the CG dot products are deterministic two-pass
-// reductions, so iterates agree with NumPy/BLAS to rounding.  The DST-II (ortho) of a row of
+// operand for operand (bit-exact operators); the solver is cg.hpp's, whose dot products fold in
+// a fixed order ("Reduction contract"), so iterates agree with NumPy/BLAS to
+// rounding.  The DST-II (ortho) of a row of
 // M values is the imaginary part of a rotated length-2M complex FFT of its odd extension
 // (rocFFT, batched over rows; the other axis through a transpose).
+#include "cg.hpp"
 #include "rocfft_util.hpp"
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 namespace rmt {
-
-constexpr int IM_BLOCKS = 1024, IM_T = 256;
-enum { IS_RZ = 0, IS_RZ_PREV = 1, IS_PQ = 2, IS_ALPHA = 3, IS_BETA = 4, IS_RR = 5, IS_N = 8 };
 
 // u-kind value at (j, i) of the full (ny, nx + 1) array, FULL: the array itself; else the
 // interior array (ny, nx - 1) embedded with zero walls (i = 0, nx): mac.py:350 np.pad
@@ -76,28 +75,16 @@ __global__ void k_im_lap_full(int kind, const double *__restrict__ f, int ny, in
     out[k] = kind == 0 ? lap_u<true>(f, j, i, ny, nx, dx2, dy2) : lap_v<true>(f, j, i, ny, nx, dx2, dy2);
 }
 
-// deterministic block partial of a per-thread sum into part[blockIdx.x]
-__device__ __forceinline__ void im_block_sum(double acc, double *part) {
-    __shared__ double sh[IM_T];
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = IM_T / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
-}
-
 // q = x - coef * Lap_hom(embed(x)) (mac.py:300-302); optional partials of x.q; R: q = b - q
 // (the initial residual r = b - A x0)
-__global__ void __launch_bounds__(IM_T) k_im_apply(int kind, const double *__restrict__ x,
+__global__ void __launch_bounds__(CG_T) k_im_apply(int kind, const double *__restrict__ x,
                                                    int ny, int nx, double dx2, double dy2,
                                                    double coef, const double *__restrict__ b,
                                                    double *__restrict__ q,
                                                    double *__restrict__ part) {
     const long n = kind == 0 ? (long)ny * (nx - 1) : (long)(ny - 1) * nx;
     double acc = 0.0;
-    for (long k = blockIdx.x * (long)IM_T + threadIdx.x; k < n; k += (long)gridDim.x * IM_T) {
+    for (long k = blockIdx.x * (long)CG_T + threadIdx.x; k < n; k += (long)gridDim.x * CG_T) {
         int j, i;
         face_of(kind, k, ny, nx, j, i);
         const double L = kind == 0 ? lap_u<false>(x, j, i, ny, nx, dx2, dy2)
@@ -106,62 +93,7 @@ __global__ void __launch_bounds__(IM_T) k_im_apply(int kind, const double *__res
         q[k] = b ? b[k] - a : a;
         acc += x[k] * a;
     }
-    if (part) im_block_sum(acc, part);
-}
-
-__global__ void __launch_bounds__(IM_T) k_im_dot(const double *__restrict__ x,
-                                                 const double *__restrict__ y, long n,
-                                                 double *__restrict__ part) {
-    double acc = 0.0;
-    for (long k = blockIdx.x * (long)IM_T + threadIdx.x; k < n; k += (long)gridDim.x * IM_T)
-        acc += x[k] * y[k];
-    im_block_sum(acc, part);
-}
-
-// the sum of the partials into sc[slot] and the CG scalar that stage derives (scipy 1.15
-// cg: beta = rho_cur / rho_prev, alpha = rho_cur / p.q, rho_prev = rho_cur)
-__global__ void __launch_bounds__(IM_T) k_im_final(const double *__restrict__ part, int slot,
-                                                   int it, double *__restrict__ sc) {
-    double acc = 0.0;
-    for (int k = threadIdx.x; k < IM_BLOCKS; k += IM_T) acc += part[k];
-    __shared__ double sh[IM_T];
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = IM_T / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x) return;
-    const double s = sh[0];
-    sc[slot] = s;
-    if (slot == IS_RZ && it > 0) sc[IS_BETA] = s / sc[IS_RZ_PREV];
-    if (slot == IS_PQ) sc[IS_ALPHA] = sc[IS_RZ] / s;
-    if (slot == IS_RR) sc[IS_RZ_PREV] = sc[IS_RZ];
-}
-
-// p = z (first iteration) or p *= beta; p += z
-__global__ void k_im_pdir(double *__restrict__ p, const double *__restrict__ z, long n,
-                          const double *__restrict__ sc, int first) {
-    const long k = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    p[k] = first ? z[k] : p[k] * sc[IS_BETA] + z[k];
-}
-
-// x += alpha p; r -= alpha q; partials of r.r
-__global__ void __launch_bounds__(IM_T) k_im_xr(double *__restrict__ x, double *__restrict__ r,
-                                                const double *__restrict__ p,
-                                                const double *__restrict__ q, long n,
-                                                const double *__restrict__ sc,
-                                                double *__restrict__ part) {
-    const double al = sc[IS_ALPHA];
-    double acc = 0.0;
-    for (long k = blockIdx.x * (long)IM_T + threadIdx.x; k < n; k += (long)gridDim.x * IM_T) {
-        x[k] = x[k] + al * p[k];
-        const double rv = r[k] - al * q[k];
-        r[k] = rv;
-        acc += rv * rv;
-    }
-    im_block_sum(acc, part);
+    if (part) cg_block_sum(acc, part);
 }
 
 // ---------------------------------------------------------------- DST-II (ortho) ---
@@ -365,42 +297,32 @@ static int helmholtz(rmt_ctx *ctx, int kind, const double *b, double coef, doubl
     if (precond) RMT_TRY(imex_plan(ctx, kind, ny, nx, dx, dy, coef, &P));
     const double dx2 = std::pow(dx, 2.0), dy2 = std::pow(dy, 2.0);
     double *w = nullptr;
-    RMT_HIP(hipMallocAsync((void **)&w, (4 * n + IM_BLOCKS + IS_N) * sizeof(double), st));
-    double *r = w, *z = w + n, *d = w + 2 * n, *q = w + 3 * n, *part = w + 4 * n;
-    double *sc = part + IM_BLOCKS;
+    RMT_HIP(hipMallocAsync((void **)&w, (4 * n + CG_WORK) * sizeof(double), st));
+    double *r = w, *z = w + n, *d = w + 2 * n, *q = w + 3 * n;
+    const CgWork W{st, n, w + 4 * n};
     int status = RMT_OK, it = 0;
     do {
         RMT_HIP(hipMemcpyAsync(x, b, n * sizeof(double), hipMemcpyDeviceToDevice, st));
-        RMT_HIP(hipMemsetAsync(part, 0, IM_BLOCKS * sizeof(double), st));
-        k_im_dot<<<IM_BLOCKS, IM_T, 0, st>>>(b, b, n, part);
-        k_im_final<<<1, IM_T, 0, st>>>(part, IS_RR, 0, sc);
+        RMT_TRY(cg_begin(W));
         double rr = 0.0;
-        RMT_HIP(hipMemcpyAsync(&rr, sc + IS_RR, sizeof(double), hipMemcpyDeviceToHost, st));
-        RMT_HIP(hipStreamSynchronize(st));
+        RMT_TRY(cg_norm2(W, b, &rr));
         const double bnrm = std::sqrt(rr), atol = rtol * bnrm;
         if (bnrm == 0.0) break;   // scipy returns b (x = b already)
         // r = b - A x0 (x0 = b is non-zero here), and r.r for the first stopping test
-        k_im_apply<<<IM_BLOCKS, IM_T, 0, st>>>(kind, x, ny, nx, dx2, dy2, coef, b, r, nullptr);
-        k_im_dot<<<IM_BLOCKS, IM_T, 0, st>>>(r, r, n, part);
-        k_im_final<<<1, IM_T, 0, st>>>(part, IS_RR, 0, sc);
-        RMT_HIP(hipMemcpyAsync(&rr, sc + IS_RR, sizeof(double), hipMemcpyDeviceToHost, st));
-        RMT_HIP(hipStreamSynchronize(st));
-        for (it = 0; it < maxiter; ++it) {
-            if (std::sqrt(rr) < atol) break;
-            if (precond) { if ((status = dst_precond(st, P, r, z))) break; }
-            const double *zz = precond ? z : r;                          // z = M r
-            k_im_dot<<<IM_BLOCKS, IM_T, 0, st>>>(r, zz, n, part);
-            k_im_final<<<1, IM_T, 0, st>>>(part, IS_RZ, it, sc);
-            k_im_pdir<<<grid1d(n, 256), 256, 0, st>>>(d, zz, n, sc, it == 0);
-            k_im_apply<<<IM_BLOCKS, IM_T, 0, st>>>(kind, d, ny, nx, dx2, dy2, coef, nullptr, q,
-                                                   part);
-            k_im_final<<<1, IM_T, 0, st>>>(part, IS_PQ, it, sc);
-            k_im_xr<<<IM_BLOCKS, IM_T, 0, st>>>(x, r, d, q, n, sc, part);
-            k_im_final<<<1, IM_T, 0, st>>>(part, IS_RR, it, sc);
-            RMT_LAUNCHED();
-            RMT_HIP(hipMemcpyAsync(&rr, sc + IS_RR, sizeof(double), hipMemcpyDeviceToHost, st));
-            RMT_HIP(hipStreamSynchronize(st));
-        }
+        k_im_apply<<<CG_BLOCKS, CG_T, 0, st>>>(kind, x, ny, nx, dx2, dy2, coef, b, r, nullptr);
+        RMT_TRY(cg_norm2(W, r, &rr));
+        status = cg_iterate(
+            W, x, r, d, q, rr, atol, maxiter,
+            [&](const double *res, const double **zz) {                      // z = M r
+                if (!precond) return (int)RMT_OK;
+                *zz = z;
+                return dst_precond(st, P, res, z);
+            },
+            [&](const double *dir, double *out, double *part) {
+                k_im_apply<<<CG_BLOCKS, CG_T, 0, st>>>(kind, dir, ny, nx, dx2, dy2, coef, nullptr,
+                                                       out, part);
+            },
+            &it);
     } while (false);
     (void)hipFreeAsync(w, st);
     if (iters) *iters = it;

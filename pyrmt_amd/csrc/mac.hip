@@ -88,32 +88,24 @@ __global__ void k_mac_centres(const double *__restrict__ u, const double *__rest
 }
 
 // big (nullable): set when a phi is NaN, infinite or >= 2^928 in magnitude (k_mac_stress)
-// one workgroup: the NaN-propagating max of G partials (NAN_MAX: nanmax, else k_reduce_p1<3>'s
-// rule -- either is exact in any order) into *out
+// one workgroup: the NaN-propagating max of G partials (NAN_MAX: nanmax, else nanmax_pick
+// -- either is exact in any order) into *out
 template <bool NAN_MAX>
 __global__ void __launch_bounds__(1024) k_max_partials(const double *__restrict__ part, int G,
                                                       double init, double *__restrict__ out) {
     __shared__ double s[1024];
+    const auto op = [](double x, double y) { return NAN_MAX ? nanmax(x, y) : nanmax_pick(x, y); };
     double acc = init;
-    for (int k = threadIdx.x; k < G; k += 1024) {
-        const double y = part[k];
-        acc = NAN_MAX ? nanmax(acc, y) : ((y > acc || y != y) ? y : acc);
-    }
+    for (int k = threadIdx.x; k < G; k += 1024) acc = op(acc, part[k]);
     s[threadIdx.x] = acc;
     __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            const double y = s[threadIdx.x + w], x = s[threadIdx.x];
-            s[threadIdx.x] = NAN_MAX ? nanmax(x, y) : ((y > x || y != y) ? y : x);
-        }
-        __syncthreads();
-    }
+    tree_fold<1024>(s, op);
     if (threadIdx.x == 0) *out = s[0];
 }
 constexpr int MP_BLOCKS = 8192;   // the fused reduction passes' workgroups (one partial each)
 
 // k_mac_centres over the whole grid on MP_BLOCKS x RED_T threads, also folding max(u_c^2 +
-// v_c^2) (NaN-propagating, k_reduce_p1<3>'s rule: a max is exact in any order) into one
+// v_c^2) (NaN-propagating, nanmax_pick: a max is exact in any order) into one
 // partial per block -- reduce_maxsq2_nan's pass over u_c, v_c saved
 // WRITE: also the centre planes (off: the advection samples the faces itself, k_sim_sl_t<1>)
 template <bool WRITE>
@@ -149,19 +141,13 @@ __global__ void __launch_bounds__(RED_T) k_mac_centres_m2(const double *__restri
             if (WRITE) { uc[c] = a; vc[c] = b; }
             fin = fin && isfinite(a) && isfinite(b);
             const double x = a * a + b * b;
-            acc = (x > acc || x != x) ? x : acc;
+            acc = nanmax_pick(acc, x);
         }
     }
     if (!fin) atomicOr(bad, 1);
     s[threadIdx.x] = acc;
     __syncthreads();
-    for (int w = RED_T / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            const double y = s[threadIdx.x + w];
-            s[threadIdx.x] = (y > s[threadIdx.x] || y != y) ? y : s[threadIdx.x];
-        }
-        __syncthreads();
-    }
+    tree_fold<RED_T>(s, nanmax_pick);
     if (threadIdx.x == 0) part[blockIdx.x] = s[0];
 }
 
@@ -211,15 +197,12 @@ __global__ void __launch_bounds__(1024) k_box_reduce(const int2 *__restrict__ br
     }
     s[0][threadIdx.x] = jmin; s[1][threadIdx.x] = jmax; s[2][threadIdx.x] = imin; s[3][threadIdx.x] = imax;
     __syncthreads();
-    for (int h = 512; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) {
-            s[0][threadIdx.x] = min(s[0][threadIdx.x], s[0][threadIdx.x + h]);
-            s[1][threadIdx.x] = max(s[1][threadIdx.x], s[1][threadIdx.x + h]);
-            s[2][threadIdx.x] = min(s[2][threadIdx.x], s[2][threadIdx.x + h]);
-            s[3][threadIdx.x] = max(s[3][threadIdx.x], s[3][threadIdx.x + h]);
-        }
-        __syncthreads();
-    }
+    tree_fold<1024>([&](int t, int u) {
+        s[0][t] = min(s[0][t], s[0][u]);
+        s[1][t] = max(s[1][t], s[1][u]);
+        s[2][t] = min(s[2][t], s[2][u]);
+        s[3][t] = max(s[3][t], s[3][u]);
+    });
     if (threadIdx.x < 4) box[threadIdx.x] = s[threadIdx.x][0];
 }
 // phi = disc_phi(X1, X2) over the grid and the support box (mac_start_boxes, a call's start in
@@ -378,13 +361,10 @@ __global__ void __launch_bounds__(MS_TPB) k_mac_stress(DiscSet D, int N, double 
     }
     smin[threadIdx.x] = jmin; smax[threadIdx.x] = jmax;
     __syncthreads();
-    for (int w = MS_TPB / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) {
-            smin[threadIdx.x] = fmin(smin[threadIdx.x], smin[threadIdx.x + w]);
-            smax[threadIdx.x] = fmax(smax[threadIdx.x], smax[threadIdx.x + w]);
-        }
-        __syncthreads();
-    }
+    tree_fold<MS_TPB>([&](int t, int u) {
+        smin[t] = fmin(smin[t], smin[u]);
+        smax[t] = fmax(smax[t], smax[u]);
+    });
     if (threadIdx.x == 0) {
         const long pb = (long)blockIdx.y * gridDim.x + blockIdx.x;
         part[2 * pb] = smin[0]; part[2 * pb + 1] = smax[0];
@@ -555,10 +535,7 @@ __global__ void __launch_bounds__(256) k_mac_rhs_rows(const double *__restrict__
     }
     s[threadIdx.x] = acc;
     __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) s[threadIdx.x] = s[threadIdx.x] + s[threadIdx.x + w];
-        __syncthreads();
-    }
+    tree_fold<256>(s, fold_add());
     if (threadIdx.x == 0) rs[j] = s[0];
 }
 
@@ -638,19 +615,13 @@ __global__ void __launch_bounds__(RED_T) k_mac_correct_um(const double *__restri
     }
     s[threadIdx.x] = acc;
     __syncthreads();
-    for (int w = RED_T / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) s[threadIdx.x] = nanmax(s[threadIdx.x], s[threadIdx.x + w]);
-        __syncthreads();
-    }
+    tree_fold<RED_T>(s, nanmax);
     if (threadIdx.x == 0) part[blockIdx.x] = s[0];
     if (!partv) return;
     __syncthreads();
     s[threadIdx.x] = accv;
     __syncthreads();
-    for (int w = RED_T / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) s[threadIdx.x] = nanmax(s[threadIdx.x], s[threadIdx.x + w]);
-        __syncthreads();
-    }
+    tree_fold<RED_T>(s, nanmax);
     if (threadIdx.x == 0) partv[blockIdx.x] = s[0];
 }
 // The next step's SL bound from the correction's face maxima (u, v unchanged since): a cell
@@ -667,13 +638,10 @@ __global__ void __launch_bounds__(1024) k_m2_bound(const double *__restrict__ pu
     for (int k = threadIdx.x; k < G; k += 1024) { a = nanmax(a, pu[k]); b = nanmax(b, pv[k]); }
     s[0][threadIdx.x] = a; s[1][threadIdx.x] = b;
     __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            s[0][threadIdx.x] = nanmax(s[0][threadIdx.x], s[0][threadIdx.x + w]);
-            s[1][threadIdx.x] = nanmax(s[1][threadIdx.x], s[1][threadIdx.x + w]);
-        }
-        __syncthreads();
-    }
+    tree_fold<1024>([&](int t, int u) {
+        s[0][t] = nanmax(s[0][t], s[0][u]);
+        s[1][t] = nanmax(s[1][t], s[1][u]);
+    });
     if (threadIdx.x == 0) {
         const double mu = s[0][0], mv = s[1][0];
         // a face above DBL_MAX / 2 may give an overflowing centre velocity (the sum of two
@@ -741,12 +709,9 @@ __global__ void __launch_bounds__(MS_TPB) k_mac_diag(DiscSet D, const double *__
     for (int k = 0; k < MD_VALS; ++k) {
         s[threadIdx.x] = acc[k];
         __syncthreads();
-        for (int w = MS_TPB / 2; w > 0; w >>= 1) {
-            if (threadIdx.x < w)
-                s[threadIdx.x] = k == 3 * MAC_MAXD ? nanmax(s[threadIdx.x], s[threadIdx.x + w])
-                                                   : s[threadIdx.x] + s[threadIdx.x + w];
-            __syncthreads();
-        }
+        tree_fold<MS_TPB>(s, [k](double x, double y) {
+            return k == 3 * MAC_MAXD ? nanmax(x, y) : x + y;
+        });
         if (threadIdx.x == 0) part[(long)blockIdx.x * MD_VALS + k] = s[0];
         __syncthreads();
     }
@@ -1287,23 +1252,19 @@ __global__ void __launch_bounds__(256) k_mac_slab_scal(const double *__restrict_
     for (int v = 0; v < 2 + 3 * K + 1; ++v) {
         // v: 0 J min, 1 J max, 2 .. 2+3K centroid sums, last max|u|
         const int kind = v == 0 ? 0 : (v == 1 || v == 2 + 3 * K) ? 1 : 2;
+        const auto op = [kind, v](double a, double x) {
+            return kind == 0 ? fmin(a, x) : kind == 1 ? (v == 1 ? fmax(a, x) : nanmax(a, x)) : a + x;
+        };
         double a = kind == 2 ? 0.0 : (kind == 0 ? 1.0 : (v == 1 ? 1.0 : 0.0));
         for (int b = t; b < MS_BLOCKS; b += 256) {
             const double x = v == 0 ? part[2 * b] : v == 1 ? part[2 * b + 1]
                            : v == 2 + 3 * K ? dp[(long)b * MD_VALS + 3 * MAC_MAXD]
                                             : dp[(long)b * MD_VALS + (v - 2)];
-            a = kind == 0 ? fmin(a, x) : kind == 1 ? (v == 1 ? fmax(a, x) : nanmax(a, x)) : a + x;
+            a = op(a, x);
         }
         s[t] = a;
         __syncthreads();
-        for (int w = 128; w > 0; w >>= 1) {
-            if (t < w) {
-                const double x = s[t + w];
-                s[t] = kind == 0 ? fmin(s[t], x)
-                     : kind == 1 ? (v == 1 ? fmax(s[t], x) : nanmax(s[t], x)) : s[t] + x;
-            }
-            __syncthreads();
-        }
+        tree_fold<256>(s, op);
         if (t == 0) {
             const int o = v == 0 ? MS_JMIN : v == 1 ? MS_JMAX : v == 2 + 3 * K ? MS_UMAX
                                                                                : MS_CEN + v - 2;

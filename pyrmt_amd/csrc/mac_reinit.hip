@@ -199,14 +199,11 @@ __device__ __forceinline__ void mr_fold(double *smx, double *smn, double *sct, d
     const int t = threadIdx.x;
     smx[t] = mx; smn[t] = mn; sct[t] = ct;
     __syncthreads();
-    for (int w = MR_T / 2; w > 0; w >>= 1) {
-        if (t < w) {
-            smx[t] = nanmax(smx[t], smx[t + w]);
-            smn[t] = mr_nanmin(smn[t], smn[t + w]);
-            sct[t] = sct[t] + sct[t + w];
-        }
-        __syncthreads();
-    }
+    tree_fold<MR_T>([&](int t, int u) {
+        smx[t] = nanmax(smx[t], smx[u]);
+        smn[t] = mr_nanmin(smn[t], smn[u]);
+        sct[t] = sct[t] + sct[u];
+    });
     mx = smx[0]; mn = smn[0]; ct = sct[0];
 }
 __global__ void __launch_bounds__(MR_T) k_mac_epoch_p1(const double *__restrict__ J,

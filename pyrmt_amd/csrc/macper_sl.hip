@@ -251,13 +251,10 @@ __global__ __launch_bounds__(256) void k_macpsl_absmax(const double *__restrict_
     }
     su[threadIdx.x] = mu; sv[threadIdx.x] = mv;
     __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            su[threadIdx.x] = nanmax(su[threadIdx.x], su[threadIdx.x + s]);
-            sv[threadIdx.x] = nanmax(sv[threadIdx.x], sv[threadIdx.x + s]);
-        }
-        __syncthreads();
-    }
+    tree_fold<256>([&](int t, int w) {
+        su[t] = nanmax(su[t], su[w]);
+        sv[t] = nanmax(sv[t], sv[w]);
+    });
     if (threadIdx.x == 0) {
         part[blockIdx.x] = su[0];
         part[SLR_BLOCKS + blockIdx.x] = sv[0];
@@ -279,13 +276,10 @@ __global__ __launch_bounds__(256) void k_macpsl_decide(const double *__restrict_
     }
     su[threadIdx.x] = mu; sv[threadIdx.x] = mv;
     __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            su[threadIdx.x] = nanmax(su[threadIdx.x], su[threadIdx.x + s]);
-            sv[threadIdx.x] = nanmax(sv[threadIdx.x], sv[threadIdx.x + s]);
-        }
-        __syncthreads();
-    }
+    tree_fold<256>([&](int t, int w) {
+        su[t] = nanmax(su[t], su[w]);
+        sv[t] = nanmax(sv[t], sv[w]);
+    });
     if (threadIdx.x == 0) {
         const double a = su[0] / dx, b = sv[0] / dy;
         const double cfl = dt * (b > a ? b : a);

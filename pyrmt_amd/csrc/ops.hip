@@ -94,7 +94,13 @@ int ensure_bytes(rmt_ctx *ctx, size_t bytes) {
 // Deterministic two-pass reductions: RED_BLOCKS fixed workgroups each fold a strided
 // slice in a fixed order, then one workgroup folds the partials in a fixed tree.
 
-template <int OP>  // 0 sum, 1 max, 2 max(a*a+b*b)
+// OP 0 sum, 1 / 2 max (NaN inputs are not on the path: guarded upstream), 3 NaN-propagating max
+template <int OP>
+__device__ __forceinline__ double red_op(double x, double y) {
+    return OP == 0 ? x + y : OP == 3 ? nanmax_pick(x, y) : fmax(x, y);
+}
+
+template <int OP>  // 0 sum, 1 max, 2 max(a*a+b*b), 3 the same, NaN-propagating
 __global__ void __launch_bounds__(RED_T) k_reduce_p1(const double *__restrict__ a,
                                                      const double *__restrict__ b, long n,
                                                      double *__restrict__ part) {
@@ -102,21 +108,11 @@ __global__ void __launch_bounds__(RED_T) k_reduce_p1(const double *__restrict__ 
     double acc = OP == 0 ? 0.0 : -INFINITY;
     for (long k = blockIdx.x * (long)RED_T + threadIdx.x; k < n; k += (long)RED_BLOCKS * RED_T) {
         double x = OP >= 2 ? a[k] * a[k] + b[k] * b[k] : a[k];
-        if (OP == 0) acc += x;
-        else if (OP == 3) acc = (x > acc || x != x) ? x : acc;   // NaN propagates
-        else acc = fmax(acc, x);   // NaN inputs are not on the path (guarded upstream)
+        acc = red_op<OP>(acc, x);
     }
     s[threadIdx.x] = acc;
     __syncthreads();
-    for (int w = RED_T / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w)
-            s[threadIdx.x] = OP == 0 ? s[threadIdx.x] + s[threadIdx.x + w]
-                             : OP == 3 ? ((s[threadIdx.x + w] > s[threadIdx.x] ||
-                                           s[threadIdx.x + w] != s[threadIdx.x + w])
-                                              ? s[threadIdx.x + w] : s[threadIdx.x])
-                                       : fmax(s[threadIdx.x], s[threadIdx.x + w]);
-        __syncthreads();
-    }
+    tree_fold<RED_T>(s, red_op<OP>);
     if (threadIdx.x == 0) part[blockIdx.x] = s[0];
 }
 
@@ -125,21 +121,10 @@ __global__ void __launch_bounds__(RED_T) k_reduce_p2(const double *__restrict__ 
                                                      double scale) {
     __shared__ double s[RED_T];
     double acc = OP == 0 ? 0.0 : -INFINITY;
-    for (int k = threadIdx.x; k < RED_BLOCKS; k += RED_T) {
-        const double y = part[k];
-        acc = OP == 0 ? acc + y : OP == 3 ? ((y > acc || y != y) ? y : acc) : fmax(acc, y);
-    }
+    for (int k = threadIdx.x; k < RED_BLOCKS; k += RED_T) acc = red_op<OP>(acc, part[k]);
     s[threadIdx.x] = acc;
     __syncthreads();
-    for (int w = RED_T / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) {
-            const double y = s[threadIdx.x + w];
-            s[threadIdx.x] = OP == 0 ? s[threadIdx.x] + y
-                             : OP == 3 ? ((y > s[threadIdx.x] || y != y) ? y : s[threadIdx.x])
-                                       : fmax(s[threadIdx.x], y);
-        }
-        __syncthreads();
-    }
+    tree_fold<RED_T>(s, red_op<OP>);
     if (threadIdx.x == 0) *out = OP == 0 ? s[0] * scale : s[0];
 }
 
@@ -190,10 +175,7 @@ __global__ void __launch_bounds__(256) k_rowsum(const double *__restrict__ x, in
     for (int i = threadIdx.x; i < nx; i += 256) acc += r[i];
     s[threadIdx.x] = acc;
     __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) s[threadIdx.x] = s[threadIdx.x] + s[threadIdx.x + w];
-        __syncthreads();
-    }
+    tree_fold<256>(s, fold_add());
     if (threadIdx.x == 0) rs[blockIdx.x] = s[0];
 }
 // k_rowsum of x = p + (pc - m) (m = *root / count, k_project_correct's mean of the raw solve),
@@ -215,10 +197,7 @@ __global__ void __launch_bounds__(256) k_rowsum_upd(double *__restrict__ p,
     }
     s[threadIdx.x] = acc;
     __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) s[threadIdx.x] = s[threadIdx.x] + s[threadIdx.x + w];
-        __syncthreads();
-    }
+    tree_fold<256>(s, fold_add());
     if (threadIdx.x == 0) rs[blockIdx.x] = s[0];
 }
 constexpr int TREE_MAX = 8192, TREE_T = 1024;
@@ -753,20 +732,18 @@ __global__ void k_project_correct(const double *__restrict__ a_s, const double *
         q = ua * ua + vb * vb;
     }
     if (m2part) {
-        // max of u^2 + v^2 over the block, NaN-propagating (k_reduce_p1<3>'s rule; a max is
+        // max of u^2 + v^2 over the block, NaN-propagating (nanmax_pick; a max is
         // exact in any order): across each wave by shuffles, then the 4 wave results
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
-            const double y = __shfl_xor(q, off);
-            if (y > q || y != y) q = y;
+            q = nanmax_pick(q, __shfl_xor(q, off));
         }
         __shared__ double s[4];
         if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = q;
         __syncthreads();
         if (threadIdx.x == 0) {
             double m = s[0];
-            for (int w = 1; w < 4; ++w)
-                if (s[w] > m || s[w] != s[w]) m = s[w];
+            for (int w = 1; w < 4; ++w) m = nanmax_pick(m, s[w]);
             m2part[(long)blockIdx.y * gridDim.x + blockIdx.x] = m;
         }
     }

@@ -30,6 +30,34 @@ inline unsigned list_grid(long max_tiles) {
 __host__ __device__ __forceinline__ double nanmax(double a, double b) {
     return (a != a || b != b) ? (a + b) : (a > b ? a : b);
 }
+// The other NaN-propagating max, folding y into x: it selects an operand and does no
+// arithmetic, so a NaN comes out with its own bits (nanmax's a + b makes a new quiet one) and
+// x stays on a tie (+-0 included).  Both are exact in any order; each reduction keeps the
+// rule it was written with, because its partials and results are compared bit for bit.
+__host__ __device__ __forceinline__ double nanmax_pick(double x, double y) {
+    return (y > x || y != y) ? y : x;
+}
+
+// The LDS pairing ladder of every block-level reduction ("Reduction contract"):
+// T threads, values already in LDS and synchronised; thread t < w folds slot t + w into slot
+// t for w = T/2, T/4, .. 1 through fold(t, t + w), which touches every array of a multi-value
+// reduction.  The result is in slot 0, visible to the whole block on return.  t: the thread's
+// index where the kernel keeps its own copy of it (k_dct1 / k_dct1s pin theirs in a register).
+template <int T, class Fold>
+__device__ __forceinline__ void tree_fold(Fold fold, int t = threadIdx.x) {
+    for (int w = T / 2; w > 0; w >>= 1) {
+        if (t < w) fold(t, t + w);
+        __syncthreads();
+    }
+}
+// one array: s[t] = op(s[t], s[t + w])
+template <int T, class V, class Op>
+__device__ __forceinline__ void tree_fold(V *s, Op op, int t = threadIdx.x) {
+    tree_fold<T>([&](int a, int b) { s[a] = op(s[a], s[b]); }, t);
+}
+struct fold_add {
+    __device__ __forceinline__ double operator()(double x, double y) const { return x + y; }
+};
 
 
 // ---------------------------------------------------------------- error plumbing --

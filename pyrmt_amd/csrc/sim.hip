@@ -637,19 +637,11 @@ __global__ void __launch_bounds__(256) k_dt_part(const double *__restrict__ part
     __shared__ bool last;
     if (e && blockIdx.x == 0 && threadIdx.x == 0) ring_record(sc, flag, e);
     double m = 0.0;
-    for (int k = blockIdx.x * 256 + threadIdx.x; k < np; k += DTP_BLOCKS * 256) {
-        const double y = part[k];
-        if (y > m || y != y) m = y;
-    }
+    for (int k = blockIdx.x * 256 + threadIdx.x; k < np; k += DTP_BLOCKS * 256)
+        m = nanmax_pick(m, part[k]);
     s[threadIdx.x] = m;
     __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            const double y = s[threadIdx.x + w];
-            if (y > s[threadIdx.x] || y != y) s[threadIdx.x] = y;
-        }
-        __syncthreads();
-    }
+    tree_fold<256>(s, nanmax_pick);
     if (threadIdx.x == 0) {
         atomicMax(acc, (unsigned long long)__double_as_longlong(s[0]));
         __threadfence();
@@ -700,6 +692,18 @@ struct DiagArgs {
     const unsigned char *fbits = nullptr, *tmark = nullptr;
 };
 // partial [sx, sy, cnt, Jmin, Jmax, ke, se, diss, ymin, ymax] per block
+// the combine of value k of that list: the minima by fmin, the maxima by fmax, the rest sums
+__device__ __forceinline__ double diag_op(int k, double x, double y) {
+    return (k == 3 || k == 8) ? fmin(x, y) : (k == 4 || k == 9) ? fmax(x, y) : x + y;
+}
+// every thread's ten values through LDS and the block tree; the results in s[k][0]
+__device__ __forceinline__ void diag_block_fold(double (*s)[DIAG_T], const double *v) {
+    for (int k = 0; k < DIAG_VALS; ++k) s[k][threadIdx.x] = v[k];
+    __syncthreads();
+    tree_fold<DIAG_T>([&](int t, int u) {
+        for (int k = 0; k < DIAG_VALS; ++k) s[k][t] = diag_op(k, s[k][t], s[k][u]);
+    });
+}
 __global__ void __launch_bounds__(DIAG_T) k_diag_p1(DiagArgs A, double *__restrict__ part) {
     __shared__ double s[DIAG_VALS][DIAG_T];
     double v[DIAG_VALS] = {0, 0, 0, INFINITY, -INFINITY, 0, 0, 0, INFINITY, -INFINITY};
@@ -747,16 +751,7 @@ __global__ void __launch_bounds__(DIAG_T) k_diag_p1(DiagArgs A, double *__restri
         if (i >= A.nx) { i -= A.nx; ++j; }
         }
     }
-    for (int k = 0; k < DIAG_VALS; ++k) s[k][threadIdx.x] = v[k];
-    __syncthreads();
-    for (int w = DIAG_T / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w)
-            for (int k = 0; k < DIAG_VALS; ++k) {
-                double x = s[k][threadIdx.x], y = s[k][threadIdx.x + w];
-                s[k][threadIdx.x] = (k == 3 || k == 8) ? fmin(x, y) : (k == 4 || k == 9) ? fmax(x, y) : x + y;
-            }
-        __syncthreads();
-    }
+    diag_block_fold(s, v);
     if (threadIdx.x < DIAG_VALS) part[blockIdx.x * DIAG_VALS + threadIdx.x] = s[threadIdx.x][0];
 }
 // k_diag_p1 (energies off) over the (row, 64-column segment) pieces that can hold a solid cell
@@ -815,16 +810,7 @@ __global__ void __launch_bounds__(DIAG_T) k_diag_seg(DiagArgs A, double *__restr
         }
     }
     if (__ballot(skipped)) { v[3] = fmin(v[3], 1.0); v[4] = fmax(v[4], 1.0); }
-    for (int k = 0; k < DIAG_VALS; ++k) s[k][threadIdx.x] = v[k];
-    __syncthreads();
-    for (int w = DIAG_T / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w)
-            for (int k = 0; k < DIAG_VALS; ++k) {
-                double x = s[k][threadIdx.x], y = s[k][threadIdx.x + w];
-                s[k][threadIdx.x] = (k == 3 || k == 8) ? fmin(x, y) : (k == 4 || k == 9) ? fmax(x, y) : x + y;
-            }
-        __syncthreads();
-    }
+    diag_block_fold(s, v);
     if (threadIdx.x < DIAG_VALS) part[blockIdx.x * DIAG_VALS + threadIdx.x] = s[threadIdx.x][0];
 }
 // the step's diagnostics partials.  Energies off and nx % 64 == 0: k_diag_seg, whether or
@@ -844,18 +830,9 @@ __global__ void __launch_bounds__(DIAG_T) k_diag_p2(const double *__restrict__ p
     for (int b = threadIdx.x; b < DIAG_BLOCKS; b += DIAG_T)
         for (int k = 0; k < DIAG_VALS; ++k) {
             double y = part[b * DIAG_VALS + k];
-            v[k] = (k == 3 || k == 8) ? fmin(v[k], y) : (k == 4 || k == 9) ? fmax(v[k], y) : v[k] + y;
+            v[k] = diag_op(k, v[k], y);
         }
-    for (int k = 0; k < DIAG_VALS; ++k) s[k][threadIdx.x] = v[k];
-    __syncthreads();
-    for (int w = DIAG_T / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w)
-            for (int k = 0; k < DIAG_VALS; ++k) {
-                double x = s[k][threadIdx.x], y = s[k][threadIdx.x + w];
-                s[k][threadIdx.x] = (k == 3 || k == 8) ? fmin(x, y) : (k == 4 || k == 9) ? fmax(x, y) : x + y;
-            }
-        __syncthreads();
-    }
+    diag_block_fold(s, v);
     if (threadIdx.x < DIAG_VALS) out[threadIdx.x] = s[threadIdx.x][0];
 }
 

@@ -314,10 +314,7 @@ __global__ void k_slab_dt(const double *__restrict__ gs, int G, double dt_const,
     }
     if (ring) { ring[0] = scal[SC_DT]; ring[1] = scal[SC_M2G]; }
     double m2 = gs[SC_M2];
-    for (int k = 1; k < G; ++k) {
-        const double x = gs[(long)k * SC_N + SC_M2];
-        if (x > m2 || x != x) m2 = x;
-    }
+    for (int k = 1; k < G; ++k) m2 = nanmax_pick(m2, gs[(long)k * SC_N + SC_M2]);
     scal[SC_M2G] = m2;
     scal[SC_DT] = fmin(dt_const, cfl * dx / (sqrt(m2) + 1e-6));
 }

@@ -6,18 +6,15 @@
 //   CG (x0 = 0, ||r|| < rtol ||b||, maxiter) scipy.sparse.linalg.cg (scipy 1.15 algorithm)
 //   p_c -= mean; a = a* - (dt / rho) dp_c/dx; BC; p = p_prev + p_c; p -= mean   :1326-1364
 //
-// The CG scalars (rho_k = r.z, p.q, alpha, beta) stay on the device; the host reads r.r once
-// per iteration for the stopping test.  Dot products are deterministic two-pass reductions
-// (fixed block partials, then one block), so a run is reproducible bit for bit; against
-// NumPy / BLAS they agree to rounding, which is the parity bar of this branch.
-#include "rmt_internal.hpp"
+// The solver is cg.hpp's; this file brings the operator (k_vr_apply), the DCT-I preconditioner
+// and the start x0 = 0.  Its reductions fold in a fixed order ("Reduction
+// contract"), so a run is reproducible bit for bit; against NumPy / BLAS the iterates agree to
+// rounding, which is the parity bar of this branch.
+#include "cg.hpp"
 #include <algorithm>
 #include <cmath>
 
 namespace rmt {
-
-constexpr int VR_BLOCKS = 1024, VR_T = 256;
-enum { VS_RZ = 0, VS_RZ_PREV = 1, VS_PQ = 2, VS_ALPHA = 3, VS_BETA = 4, VS_RR = 5, VS_N = 8 };
 
 // 1.0 / rho (functions.py:1305)
 __global__ void k_vr_inv(const double *__restrict__ rho, long n, double *__restrict__ ir) {
@@ -75,87 +72,19 @@ __device__ __forceinline__ double vr_apply(const double *__restrict__ p,
     return res;
 }
 
-// block partial of sum x*y (fixed grid: deterministic)
-__device__ __forceinline__ void vr_block_sum(double v, double *part) {
-    __shared__ double sh[VR_T];
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = VR_T / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
-}
-
 // out = A p (the operator only, rmt_apply_variable_poisson) or q = A p and partials of p.q
-__global__ void __launch_bounds__(VR_T) k_vr_apply(const double *__restrict__ p,
+__global__ void __launch_bounds__(CG_T) k_vr_apply(const double *__restrict__ p,
                                                    const double *__restrict__ ir, int ny, int nx,
                                                    double cx, double cy, double *__restrict__ q,
                                                    double *__restrict__ part) {
     double acc = 0.0;
     const long n = (long)ny * nx;
-    for (long c = blockIdx.x * (long)VR_T + threadIdx.x; c < n; c += (long)gridDim.x * VR_T) {
+    for (long c = blockIdx.x * (long)CG_T + threadIdx.x; c < n; c += (long)gridDim.x * CG_T) {
         const double v = vr_apply(p, ir, c, (int)(c / nx), (int)(c % nx), ny, nx, cx, cy);
         q[c] = v;
         acc += p[c] * v;
     }
-    if (part) vr_block_sum(acc, part);
-}
-
-__global__ void __launch_bounds__(VR_T) k_vr_dot(const double *__restrict__ x,
-                                                 const double *__restrict__ y, long n,
-                                                 double *__restrict__ part) {
-    double acc = 0.0;
-    for (long c = blockIdx.x * (long)VR_T + threadIdx.x; c < n; c += (long)gridDim.x * VR_T)
-        acc += x[c] * y[c];
-    vr_block_sum(acc, part);
-}
-
-// the final sum of the partials into sc[slot], then the derived scalar of that stage:
-// slot VS_RZ: beta = rz / rz_prev (iteration > 0); VS_PQ: alpha = rz / pq;
-// VS_RR: rz_prev = rz
-__global__ void __launch_bounds__(VR_T) k_vr_final(const double *__restrict__ part, int slot,
-                                                   int it, double *__restrict__ sc) {
-    double acc = 0.0;
-    for (int k = threadIdx.x; k < VR_BLOCKS; k += VR_T) acc += part[k];
-    __shared__ double sh[VR_T];
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = VR_T / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x) return;
-    const double s = sh[0];
-    sc[slot] = s;
-    if (slot == VS_RZ && it > 0) sc[VS_BETA] = s / sc[VS_RZ_PREV];
-    if (slot == VS_PQ) sc[VS_ALPHA] = sc[VS_RZ] / s;
-    if (slot == VS_RR) sc[VS_RZ_PREV] = sc[VS_RZ];
-}
-
-// p = z (first iteration) or p = p * beta + z  (p *= beta; p += z)
-__global__ void k_vr_pdir(double *__restrict__ p, const double *__restrict__ z, long n,
-                          const double *__restrict__ sc, int first) {
-    const long k = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    p[k] = first ? z[k] : p[k] * sc[VS_BETA] + z[k];
-}
-
-// x += alpha p; r -= alpha q; partials of r.r
-__global__ void __launch_bounds__(VR_T) k_vr_xr(double *__restrict__ x, double *__restrict__ r,
-                                                const double *__restrict__ p,
-                                                const double *__restrict__ q, long n,
-                                                const double *__restrict__ sc,
-                                                double *__restrict__ part) {
-    const double al = sc[VS_ALPHA];
-    double acc = 0.0;
-    for (long c = blockIdx.x * (long)VR_T + threadIdx.x; c < n; c += (long)gridDim.x * VR_T) {
-        x[c] = x[c] + al * p[c];
-        const double rv = r[c] - al * q[c];
-        r[c] = rv;
-        acc += rv * rv;
-    }
-    vr_block_sum(acc, part);
+    if (part) cg_block_sum(acc, part);
 }
 
 // a = a* - (dt / rho) dpc/dx at the BC source cell (functions.py:1350-1356), p = p_prev + pc
@@ -197,7 +126,7 @@ int rmt_apply_variable_poisson(rmt_ctx *ctx, const double *p, double dx, double 
     RMT_CHECK(ctx && p && inv_rho && out && ctx->ny >= 2 && ctx->nx >= 2, RMT_EINVAL,
               "bad argument");
     const int ny = ctx->ny, nx = ctx->nx;
-    k_vr_apply<<<std::min<long>(VR_BLOCKS, grid1d((long)ny * nx, VR_T)), VR_T, 0, ctx->stream>>>(
+    k_vr_apply<<<std::min<long>(CG_BLOCKS, grid1d((long)ny * nx, CG_T)), CG_T, 0, ctx->stream>>>(
         p, inv_rho, ny, nx, 1.0 / std::pow(dx, 2.0), 1.0 / std::pow(dy, 2.0), out, nullptr);
     RMT_LAUNCHED();
     return RMT_OK;
@@ -228,10 +157,10 @@ int rmt_pressure_projection_variable(rmt_ctx *ctx, const double *a_star, const d
     hipStream_t st = ctx->stream;
     // workspace: ir, rhs/r, x, z, dir, q, partials + scalars
     double *w = nullptr;
-    RMT_HIP(hipMallocAsync((void **)&w, (6 * n + VR_BLOCKS + VS_N) * sizeof(double), st));
+    RMT_HIP(hipMallocAsync((void **)&w, (6 * n + CG_WORK) * sizeof(double), st));
     double *ir = w, *r = w + n, *x = w + 2 * n, *z = w + 3 * n, *d = w + 4 * n, *q = w + 5 * n;
-    double *part = w + 6 * n, *sc = part + VR_BLOCKS;
-    const unsigned g = grid1d(n, 256), gr = VR_BLOCKS;   // reductions: every partial written
+    const CgWork W{st, n, w + 6 * n};
+    const unsigned g = grid1d(n, 256);
     int status = RMT_OK, it = 0;
     do {
         k_vr_inv<<<g, 256, 0, st>>>(rho, n, ir);
@@ -243,31 +172,23 @@ int rmt_pressure_projection_variable(rmt_ctx *ctx, const double *a_star, const d
         }
         if ((status = sub_mean_rows(ctx, r, ny, nx))) break;   // rhs -= mean(rhs)
         RMT_HIP(hipMemsetAsync(x, 0, n * sizeof(double), st));
-        RMT_HIP(hipMemsetAsync(part, 0, VR_BLOCKS * sizeof(double), st));
+        RMT_TRY(cg_begin(W));
         // ||b||: scipy's atol = rtol * ||b|| (x0 = 0, r = b)
-        k_vr_dot<<<VR_BLOCKS, VR_T, 0, st>>>(r, r, n, part);
-        k_vr_final<<<1, VR_T, 0, st>>>(part, VS_RR, 0, sc);
         double rr = 0.0;
-        RMT_HIP(hipMemcpyAsync(&rr, sc + VS_RR, sizeof(double), hipMemcpyDeviceToHost, st));
-        RMT_HIP(hipStreamSynchronize(st));
+        RMT_TRY(cg_norm2(W, r, &rr));
         const double bnrm = std::sqrt(rr), atol = rtol * bnrm;
         const double cx = 1.0 / std::pow(dx, 2.0), cy = 1.0 / std::pow(dy, 2.0);
         if (bnrm != 0.0) {
-            for (it = 0; it < maxiter; ++it) {
-                if (std::sqrt(rr) < atol) break;
-                if ((status = dct_solve(ctx, r, dx, dy, z))) break;          // z = M r
-                k_vr_dot<<<VR_BLOCKS, VR_T, 0, st>>>(r, z, n, part);
-                k_vr_final<<<1, VR_T, 0, st>>>(part, VS_RZ, it, sc);
-                k_vr_pdir<<<g, 256, 0, st>>>(d, z, n, sc, it == 0);
-                k_vr_apply<<<gr, VR_T, 0, st>>>(d, ir, ny, nx, cx, cy, q, part);
-                k_vr_final<<<1, VR_T, 0, st>>>(part, VS_PQ, it, sc);
-                k_vr_xr<<<gr, VR_T, 0, st>>>(x, r, d, q, n, sc, part);
-                k_vr_final<<<1, VR_T, 0, st>>>(part, VS_RR, it, sc);
-                RMT_LAUNCHED();
-                RMT_HIP(hipMemcpyAsync(&rr, sc + VS_RR, sizeof(double), hipMemcpyDeviceToHost,
-                                       st));
-                RMT_HIP(hipStreamSynchronize(st));
-            }
+            status = cg_iterate(
+                W, x, r, d, q, rr, atol, maxiter,
+                [&](const double *res, const double **zz) {                  // z = M r
+                    *zz = z;
+                    return dct_solve(ctx, res, dx, dy, z);
+                },
+                [&](const double *dir, double *out, double *part) {
+                    k_vr_apply<<<CG_BLOCKS, CG_T, 0, st>>>(dir, ir, ny, nx, cx, cy, out, part);
+                },
+                &it);
             if (status) break;
         }
         // bnrm == 0: scipy returns b (all zeros) -- x is zero already

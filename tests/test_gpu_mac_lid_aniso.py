@@ -5,7 +5,7 @@ dy**2) at a host call site, in imex_plan's eigenvalues, in the lid term, in the 
 the projection's correction passes every one of those; it fails here.
 
 Against the reference's fixture (tests/golden/mac_lid_aniso.npz: N = 5, 6, 33) and, at N = 64
-and 97 (and 516 once, where the grid-stride loops of k_im_apply / k_im_dot / k_im_xr take their
+and 97 (and 516 once, where the grid-stride loops of k_im_apply / k_cg_dot / k_cg_xr take their
 second trip), against the oracle, which tests/test_mac_lid_aniso_cpu.py pins to that fixture
 bit for bit.  The projection's oracle sizes are 64 and 99: the DCT-II solve refuses the prime
 97 (radices <= 23), which is asserted.
@@ -258,8 +258,8 @@ def test_helmholtz_vs_oracle(M, MO, N, box):
 
 
 def test_helmholtz_grid_stride_second_trip(M, MO):
-    """N = 516: 516 * 515 interior values against the 262144 threads of k_im_apply, k_im_dot and
-    k_im_xr, so their loops run a second trip."""
+    """N = 516: 516 * 515 interior values against the 262144 threads of k_im_apply, k_cg_dot and
+    k_cg_xr, so their loops run a second trip."""
     for case in A.HELM_BIG:
         assert case[0] * (case[0] - 1) > 1024 * 256
         _helm_case(M, MO, case)

@@ -77,6 +77,70 @@ def test_variable_projection_iterations_vs_oracle(gpu, monkeypatch, N, ratio, ma
         np.testing.assert_allclose(got, ref, rtol=0, atol=1e-10 * max(np.abs(ref).max(), 1.0))
 
 
+def _project(monkeypatch, N, ratio, maxiter, rtol=None, with_prev=True, zero=False):
+    """(GPU a, b, p, iterations), (oracle a, b, p, iterations) of one projection of _case."""
+    from oracle import oracle as O
+    from pyrmt_amd import functions as F
+    from pyrmt_amd.bc import FreeSlipBox
+    dx, dy, rho, a, b, p_prev = _case(N, ratio)
+    if zero:
+        a, b = np.zeros_like(a), np.zeros_like(b)
+    if not with_prev:
+        p_prev = None
+    eig = O._precompute_poisson_eigenvalues(N, N, dx, dy)
+    dt = 1e-3
+    monkeypatch.setattr(F, "CG_MAXITER", maxiter)
+    if rtol is not None:
+        monkeypatch.setattr(F, "CG_RTOL", rtol)
+    ref = O.pressure_projection_variable(a, b, dx, dy, dt, rho, 2, 0.0, p_prev, eig,
+                                         rtol=F.CG_RTOL, maxiter=maxiter)
+    ga, gb, gp, _, _ = F.pressure_projection_amg(a, b, dx, dy, dt, rho, FreeSlipBox(),
+                                                 p_prev=p_prev, eigenvalues=eig)
+    return (ga, gb, gp, F.last_cg_iterations), ref
+
+
+def _assert_fields(got, ref):
+    for g, r in zip(got[:3], ref[:3]):
+        np.testing.assert_allclose(g, r, rtol=0, atol=1e-10 * max(np.abs(r).max(), 1.0))
+
+
+@pytest.mark.parametrize("with_prev", [True, False])
+@pytest.mark.parametrize("N,ratio,rtol", [(17, 4.0, 1e-2), (33, 4.0, 2e-2)])
+def test_variable_projection_convergence_exit(gpu, monkeypatch, N, ratio, rtol, with_prev):
+    """The stopping test ends the solve below the cap, at the oracle's iteration.  The oracle's
+    relative residual at its last failing test and at the passing one is 0.018 / 0.0063
+    (N = 17, 5 iterations) and 0.035 / 0.010 (N = 33, 4 iterations): a factor >= 1.6 either
+    side of rtol, so the summation order cannot move the count."""
+    from pyrmt_amd import functions as F
+    got, ref = _project(monkeypatch, N, ratio, F.CG_MAXITER, rtol=rtol, with_prev=with_prev)
+    assert got[3] == ref[3] < F.CG_MAXITER
+    _assert_fields(got, ref)
+
+
+def test_variable_projection_zero_rhs(gpu, monkeypatch):
+    """||b|| = 0: no iteration, x = 0, so zero velocities and pressure come back."""
+    from pyrmt_amd import functions as F
+    got, ref = _project(monkeypatch, 17, 4.0, F.CG_MAXITER, with_prev=False, zero=True)
+    assert got[3] == ref[3] == 0
+    for g in got[:3]:
+        np.testing.assert_array_equal(g, np.zeros((17, 17)))
+
+
+def test_variable_projection_maxiter_zero(gpu, monkeypatch):
+    got, ref = _project(monkeypatch, 17, 4.0, 0)
+    assert got[3] == ref[3] == 0
+    _assert_fields(got, ref)
+
+
+def test_variable_projection_repeats_bitwise(gpu, monkeypatch):
+    """Every reduction of the solver folds in a fixed order: the same call, the same bits."""
+    first, _ = _project(monkeypatch, 17, 4.0, 5)
+    again, _ = _project(monkeypatch, 17, 4.0, 5)
+    assert first[3] == again[3] == 5
+    for x, y in zip(first[:3], again[:3]):
+        np.testing.assert_array_equal(x, y)
+
+
 def test_variable_projection_reference_fixture(gpu):
     """The reference's own projection on the fixture runs all 200 CG iterations without
     converging (|p| ~ 1e8: the iteration amplifies the rhs component outside the operator's
