@@ -675,6 +675,31 @@ int rmt_mac_total_force(rmt_ctx *ctx, const double *X1, const double *X2,
  * cells over phi <= 0 (-inf, +inf, 0 when there is none). */
 int rmt_mac_epoch_distortion(rmt_ctx *ctx, const double *J_ep, const double *phi, double *out3);
 
+/* ---- soft disc under the integrator ladder (benchmarks/mac_soft_disc_lid.py:79-150,
+ * mac_soft.hip).  Planes are (ny, nx) of the context, u / fu (ny, nx+1), v / fv (ny+1, nx);
+ * dx, dy are arguments: nothing assumes a square grid or box. ---- */
+/* :103-110 in one launch: solid_cauchy_stress (w_cut = 0) and its J, the blend with
+ * 1 - smoothed_heaviside(phi, w_t), the central divergence (rmt_grad_x_2nd / rmt_grad_y_2nd),
+ * the average to the interior faces, wall faces 0.  The same bits as those operators composed;
+ * the blended stress stays in LDS. */
+int rmt_mac_solid_force(rmt_ctx *ctx, const double *X1, const double *X2, const double *phi,
+                        double dx, double dy, double w_t, double mu_s, double kappa,
+                        double detg_clamp, int isochoric, double *fu, double *fv, double *J);
+/* :133-134: um = 0.5 (u0 + u1), uc = 0.5 (um[:, :-1] + um[:, 1:]), likewise v; with u0 == u1
+ * and v0 == v1 the plain face-to-centre average of :82-83 (0.5 (u + u) is u). */
+int rmt_mac_midpoint_centres(rmt_ctx *ctx, const double *u0, const double *v0, const double *u1,
+                             const double *v1, double *uc, double *vc);
+/* :139-150: out8 (device, 8 doubles) = the number of phi <= 0 cells, the sums of Xc and Yc over
+ * them (cell centres (i + 0.5) dx, (j + 0.5) dy), min J and max J over the plane, max|u|,
+ * max|v| (NaN propagates in all four) and 1.0 if u or v holds a non-finite value, else 0.0. */
+int rmt_mac_soft_diag(rmt_ctx *ctx, const double *phi, const double *J, const double *u,
+                      const double *v, double dx, double dy, double *out8);
+/* mac.py:698-721: SSP-RK3 of -H div(u xi) with the face velocity, H = (phi <= w_cut); three
+ * launches over two scratch planes of the context.  out must not be xi. */
+int rmt_mac_advect_xi_conservative(rmt_ctx *ctx, const double *xi, const double *u,
+                                   const double *v, double dx, double dy, double dt,
+                                   const double *phi, double w_cut, double *out);
+
 /* The MAC step decomposed into row slabs (config 5 on several GPUs).
  * No reference interface: pyRMT runs mac_multi_disc_lid.py:62-98 in one process.  Slab
  * `rank` of G owns cell rows [row_splits[rank], row_splits[rank+1]) (even, > RMT_SLAB_HALO

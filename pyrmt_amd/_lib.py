@@ -226,6 +226,11 @@ SIGNATURES = {
     "rmt_mac_total_stress": (_I, [_P, _P, _P, _P, _P, _D, _D, _D, _D, _P, _P, _P, _P, _P]),
     "rmt_mac_total_force": (_I, [_P, _P, _P, _P, _P, _D, _D, _D, _D, _P, _P, _P]),
     "rmt_mac_epoch_distortion": (_I, [_P, _P, _P, _P]),
+    # soft disc under the integrator ladder (mac.py MacSoftDisc, mac_soft.hip)
+    "rmt_mac_solid_force": (_I, [_P, _P, _P, _P, _D, _D, _D, _D, _D, _D, _I, _P, _P, _P]),
+    "rmt_mac_midpoint_centres": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "rmt_mac_soft_diag": (_I, [_P, _P, _P, _P, _P, _D, _D, _P]),
+    "rmt_mac_advect_xi_conservative": (_I, [_P, _P, _P, _P, _D, _D, _D, _P, _D, _P]),
 }
 
 _lib = None

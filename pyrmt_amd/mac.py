@@ -17,6 +17,9 @@ The free-slip box (mac.py:179-193, 656-689): ``momentum_predictor_freeslip``,
 Reference-map reinitialisation with stored deformation (benchmarks/mac_reinit_test.py,
 mac_reinit.hip): ``total_stress``, ``total_force``, ``epoch_distortion`` and the loop
 ``MacReinitDisc`` / ``mac_reinit_run``, composed from operators on device tensors.
+The soft disc under the integrator ladder (benchmarks/mac_soft_disc_lid.py, mac.py:43-78,
+698-721, mac_soft.hip): ``resolve_integrator``, ``solid_force``, ``midpoint_centres``,
+``soft_diag``, ``advect_xi_conservative`` and the loop ``MacSoftDisc`` / ``mac_soft_disc_run``.
 """
 import ctypes
 import math
@@ -245,10 +248,8 @@ def _pcg_helmholtz(rhs_int, apply_lap_hom, embed, coef, dx, dy, rtol=1e-8, maxit
     return x
 
 
-def momentum_predictor_lid_imex(u, v, nu, dx, dy, dt, U_lid, fu=None, fv=None, rho=1.0,
-                                rtol=1e-8, cs2=0.0):
-    """mac.py:319-369: explicit central advection + face forces, implicit (backward-Euler)
-    viscosity (+ the trapezoidal elastic term, cs2 > 0) by DST-preconditioned CG."""
+def _predictor_lid_imex(u, v, nu, dx, dy, dt, U_lid, fu, fv, rho, rtol, cs2):
+    """momentum_predictor_lid_imex with the two PCG iteration counts: (u*, v*, (it_u, it_v))."""
     N = _lid_n("momentum_predictor_lid_imex", u, v, fu, fv)
     io = _IO(u, v); ud = io.dev(u); vd = io.dev(v)
     fud, fvd = io.dev(fu), io.dev(fv)
@@ -258,7 +259,32 @@ def momentum_predictor_lid_imex(u, v, nu, dx, dy, dt, U_lid, fu=None, fv=None, r
         _ctx(N), _p(ud), _p(vd), float(nu), float(dx), float(dy), float(dt),
         float(U_lid), _p(fud), _p(fvd), float(rho), float(rtol), float(cs2), _p(us), _p(vs),
         ctypes.cast(it, ctypes.c_void_p)), "momentum_predictor_lid_imex")
-    return io.out(us), io.out(vs)
+    return io.out(us), io.out(vs), (it[0], it[1])
+
+
+def momentum_predictor_lid_imex(u, v, nu, dx, dy, dt, U_lid, fu=None, fv=None, rho=1.0,
+                                rtol=1e-8, cs2=0.0):
+    """mac.py:319-369: explicit central advection + face forces, implicit (backward-Euler)
+    viscosity (+ the trapezoidal elastic term, cs2 > 0) by DST-preconditioned CG."""
+    return _predictor_lid_imex(u, v, nu, dx, dy, dt, U_lid, fu, fv, rho, rtol, cs2)[:2]
+
+
+def _predictor_lid_semilag(u, v, nu, dx, dy, dt, U_lid, fu, fv, rho, cs2, rtol, cfl_switch):
+    """momentum_predictor_lid_semilag with the PCG counts and the branch taken:
+    (u*, v*, (it_u, it_v), semi-Lagrangian)."""
+    N = _lid_n("momentum_predictor_lid_semilag", u, v, fu, fv)
+    io = _IO(u, v); ud = io.dev(u); vd = io.dev(v)
+    cfl = dt * max(float(ud.abs().max()) / dx, float(vd.abs().max()) / dy)
+    if cfl <= cfl_switch:
+        return _predictor_lid_imex(u, v, nu, dx, dy, dt, U_lid, fu, fv, rho, rtol, cs2) + (False,)
+    fud, fvd = io.dev(fu), io.dev(fv)
+    us = io.empty(ud.shape); vs = io.empty(vd.shape)
+    it = (ctypes.c_int * 2)()
+    L.check(L.lib().rmt_mac_momentum_predictor_lid_semilag(
+        _ctx(N), _p(ud), _p(vd), float(nu), float(dx), float(dy), float(dt),
+        float(U_lid), _p(fud), _p(fvd), float(rho), float(cs2), float(rtol), _p(us), _p(vs),
+        ctypes.cast(it, ctypes.c_void_p)), "momentum_predictor_lid_semilag")
+    return io.out(us), io.out(vs), (it[0], it[1]), True
 
 
 def momentum_predictor_lid_semilag(u, v, nu, dx, dy, dt, U_lid, fu=None, fv=None, rho=1.0,
@@ -267,20 +293,8 @@ def momentum_predictor_lid_semilag(u, v, nu, dx, dy, dt, U_lid, fu=None, fv=None
     CFL <= cfl_switch (mac.py:387-390), else the semi-Lagrangian midpoint backtrace through
     cubic-spline interpolation (map_coordinates order 3, 'nearest') and the same PCG
     viscosity solve."""
-    N = _lid_n("momentum_predictor_lid_semilag", u, v, fu, fv)
-    io = _IO(u, v); ud = io.dev(u); vd = io.dev(v)
-    cfl = dt * max(float(ud.abs().max()) / dx, float(vd.abs().max()) / dy)
-    if cfl <= cfl_switch:
-        return momentum_predictor_lid_imex(u, v, nu, dx, dy, dt, U_lid, fu=fu, fv=fv, rho=rho,
-                                           rtol=rtol, cs2=cs2)
-    fud, fvd = io.dev(fu), io.dev(fv)
-    us = io.empty(ud.shape); vs = io.empty(vd.shape)
-    it = (ctypes.c_int * 2)()
-    L.check(L.lib().rmt_mac_momentum_predictor_lid_semilag(
-        _ctx(N), _p(ud), _p(vd), float(nu), float(dx), float(dy), float(dt),
-        float(U_lid), _p(fud), _p(fvd), float(rho), float(cs2), float(rtol), _p(us), _p(vs),
-        ctypes.cast(it, ctypes.c_void_p)), "momentum_predictor_lid_semilag")
-    return io.out(us), io.out(vs)
+    return _predictor_lid_semilag(u, v, nu, dx, dy, dt, U_lid, fu, fv, rho, cs2, rtol,
+                                  cfl_switch)[:2]
 
 
 def momentum_predictor_freeslip(u, v, nu, dx, dy, dt, fu=None, fv=None, rho=1.0):
@@ -1150,3 +1164,316 @@ def mac_reinit_run(N=96, t_end=15.0, reinit=True, U_lid=1.0, mu_s=0.3, mu_f=0.01
     sim = MacReinitDisc(N, reinit, U_lid, mu_s, mu_f, rho, reinit_J)
     sim.step(2**31 - 1, t_end)
     return (sim.t, sim) if return_sim else sim.t
+
+
+# ------------------------------------------------------------------ integrator ladder --
+# benchmarks/mac_soft_disc_lid.py (the soft disc against Sugiyama 2011) under the reference's
+# one-knob ladder explicit -> imex -> imex-elastic, each with an optional "-sl" suffix
+# (mac.py:25-78), through mac_soft.hip.
+INTEGRATORS = ("explicit", "imex", "imex-elastic")
+
+
+def resolve_integrator(integrator=None, imex=False, elastic_imex=False, implicit_visc=False,
+                       supports_elastic=True):
+    """mac.py:46-78 (host): (canonical name, use_imex, use_elastic) of a unified `integrator=`
+    name (aliases accepted) or, with None, of the legacy booleans."""
+    if integrator is None:
+        name = "imex-elastic" if elastic_imex else "imex" if (imex or implicit_visc) else "explicit"
+    else:
+        key = str(integrator).lower().replace("_", "-").strip()
+        aliases = {
+            "explicit": "explicit", "exp": "explicit", "forward-euler": "explicit",
+            "imex": "imex", "imex-visc": "imex", "implicit-viscosity": "imex",
+            "semi-implicit": "imex",
+            "imex-elastic": "imex-elastic", "elastic": "imex-elastic",
+            "implicit-elastic": "imex-elastic",
+        }
+        if key not in aliases:
+            raise ValueError(f"unknown integrator {integrator!r}; choose from {INTEGRATORS}")
+        name = aliases[key]
+    if name == "imex-elastic" and not supports_elastic:
+        raise ValueError("integrator='imex-elastic' is not available for this driver "
+                         "(no solid-stress force path); use 'explicit' or 'imex'")
+    return name, name in ("imex", "imex-elastic"), name == "imex-elastic"
+
+
+def _faces2(what, shape, u, v):
+    ny, nx = shape
+    got = (tuple(np.shape(u)), tuple(np.shape(v)))
+    if got != ((ny, nx + 1), (ny + 1, nx)):
+        raise ValueError(f"{what}: u (Ny, Nx+1) and v (Ny+1, Nx) of the {shape} cells; got {got}")
+
+
+def _stencil_shape(what, **planes):
+    shape = _plane2(what, **planes)
+    if min(shape) < 5:
+        raise ValueError(f"{what}: Ny, Nx >= 5 (the one-sided edge stencils); got {shape}")
+    return shape
+
+
+def solid_force(X1, X2, phi, dx, dy, w_t, mu_s, kappa=0.0, detg_clamp=0.0, isochoric=False):
+    """mac_soft_disc_lid.py:103-110 in one launch: (fu (Ny, Nx+1), fv (Ny+1, Nx), J), the face
+    forces of the neo-Hookean stress of solid_cauchy_stress (w_cut = 0) blended with
+    1 - smoothed_heaviside(phi, w_t): central divergence, averaged to the interior faces, wall
+    faces 0.  The same bits as those operators composed."""
+    ny, nx = _stencil_shape("solid_force", X1=X1, X2=X2, phi=phi)
+    io = _IO(X1, X2, phi); X1d, X2d, pd = map(io.dev, (X1, X2, phi))
+    fu = io.empty((ny, nx + 1)); fv = io.empty((ny + 1, nx)); J = io.empty((ny, nx))
+    L.check(L.lib().rmt_mac_solid_force(ctx_for(ny, nx).bind(), _p(X1d), _p(X2d), _p(pd),
+                                        float(dx), float(dy), float(w_t), float(mu_s),
+                                        float(kappa), float(detg_clamp), int(bool(isochoric)),
+                                        _p(fu), _p(fv), _p(J)), "solid_force")
+    return io.out(fu), io.out(fv), io.out(J)
+
+
+def midpoint_centres(u0, v0, u1, v1):
+    """mac_soft_disc_lid.py:133-134: the mean of two face velocities averaged to the cell
+    centres, (uc, vc); with u1 is u0 and v1 is v0 the plain average of :82-83."""
+    shape = (np.shape(u0)[0], np.shape(v0)[1]) if np.ndim(u0) == 2 and np.ndim(v0) == 2 else ()
+    if len(shape) != 2 or min(shape) < 2:
+        raise ValueError("midpoint_centres: u (Ny, Nx+1) and v (Ny+1, Nx) faces")
+    _faces2("midpoint_centres", shape, u0, v0)
+    _faces2("midpoint_centres", shape, u1, v1)
+    io = _IO(u0, v0, u1, v1); u0d, v0d = io.dev(u0), io.dev(v0)
+    u1d = u0d if u1 is u0 else io.dev(u1); v1d = v0d if v1 is v0 else io.dev(v1)
+    uc = io.empty(shape); vc = io.empty(shape)
+    L.check(L.lib().rmt_mac_midpoint_centres(_pctx(shape, True), _p(u0d), _p(v0d), _p(u1d),
+                                             _p(v1d), _p(uc), _p(vc)), "midpoint_centres")
+    return io.out(uc), io.out(vc)
+
+
+def soft_diag(phi, J, u, v, dx, dy, out=None):
+    """What mac_soft_disc_lid.py:139-150 reads, in one reduction, as eight doubles (a device
+    tensor for device inputs, written into `out` when given): the number of phi <= 0 cells, the
+    sums of Xc and Yc over them, min J, max J, max|u|, max|v| (NaN propagates as in
+    ndarray.min / max) and 1.0 if u or v holds a non-finite value."""
+    shape = _plane2("soft_diag", phi=phi, J=J)
+    _faces2("soft_diag", shape, u, v)
+    io = _IO(phi, J, u, v); pd, Jd, ud, vd = map(io.dev, (phi, J, u, v))
+    o = io.empty((8,)) if out is None else out
+    L.check(L.lib().rmt_mac_soft_diag(_pctx(shape, True), _p(pd), _p(Jd), _p(ud), _p(vd),
+                                      float(dx), float(dy), _p(o)), "soft_diag")
+    return io.out(o)
+
+
+def advect_xi_conservative(xi, u, v, dx, dy, dt, phi, w_cut=0.0):
+    """mac.py:713-721: SSP-RK3 of -H div(u xi) for a cell-centred map component with the MAC
+    face velocity (Jain 2019, eq. 26), H = (phi <= w_cut); the reference's bits."""
+    shape = _plane2("advect_xi_conservative", xi=xi, phi=phi)
+    _faces2("advect_xi_conservative", shape, u, v)
+    io = _IO(xi, u, v, phi); xd, ud, vd, pd = map(io.dev, (xi, u, v, phi))
+    out = io.empty(shape)
+    L.check(L.lib().rmt_mac_advect_xi_conservative(_pctx(shape, True), _p(xd), _p(ud), _p(vd),
+                                                   float(dx), float(dy), float(dt), _p(pd),
+                                                   float(w_cut), _p(out)),
+            "advect_xi_conservative")
+    return io.out(out)
+
+
+class MacSoftDisc:
+    """The loop body of benchmarks/mac_soft_disc_lid.py:79-150 on device tensors, composed from
+    operators (no fused step): the soft disc (R 0.2 at (0.6, 0.5), kappa 0, rho 1, mu_f 0.01,
+    w_t = 2 dx, U_lid 1, 3 extrapolation layers) under the integrator ladder.
+
+    explicit / imex (and imex-sl): phi from the map, both map components advected with the
+    centre velocity and masked with that phi, extrapolated, phi again, the face forces in one
+    launch (rmt_mac_solid_force), predictor, projection.  imex-elastic (and imex-elastic-sl):
+    forces from the un-advected map, the predictor with cs2 = mu_s / rho, projection, then the
+    map advanced with the midpoint velocity of the old and new faces; phi and mask are the
+    step's first.  The "-sl" rungs go through momentum_predictor_lid_semilag's CFL switch.
+    One reduction (rmt_mac_soft_diag) feeds the stop test and the record: the host reads its
+    eight doubles once a step (the -sl rungs also read the CFL, the IMEX solves r.r).  The stop
+    test of :139-147 (no solid cell, non-finite u or v, min J < 0, max J > 20) comes before
+    t += dt: a diverging step leaves no row and sets `diverged`.  dt is not clipped to t_end.
+    The semi-Lagrangian map advection skips the non-finite-velocity guard: the loop stops on a
+    non-finite velocity before the next step reads it.
+
+    `record`: one (t, cx, cy, min J, max J) per step; `sl_steps`: the steps that took the
+    semi-Lagrangian branch; `pcg_iters`: the last step's two PCG counts."""
+
+    X0, Y0, R = 0.6, 0.5, 0.2
+    KAPPA, RHO, MU_F, U_LID, LAYERS = 0.0, 1.0, 0.01, 1.0, 3
+    STATE = ("u", "v", "X1", "X2", "t")
+    SCHEMES = ("semilagrangian", "semilagrangian_cubic", "central2", "weno5")
+
+    def __init__(self, N=128, integrator=None, imex=False, dt=None, mu_s=0.1,
+                 scheme="semilagrangian", w_cut_fac=0.0, detg_clamp=0.0, isochoric=False,
+                 reinit=False):
+        name, self.use_semilag, self.use_imex, self.use_elastic = self.parse_integrator(
+            integrator, imex)
+        self.integrator = name
+        if scheme == "conservative" or reinit:
+            raise NotImplementedError(
+                "MacSoftDisc: scheme='conservative' and reinit=True need the reference's FMM "
+                "level-set reinitialisation (scikit-fmm), which is not part of this build")
+        if scheme not in self.SCHEMES:
+            raise ValueError("Unknown advection scheme %r (expected one of %s)"
+                             % (scheme, ", ".join(self.SCHEMES)))
+        if scheme in ("central2", "weno5") and w_cut_fac == 0.0:
+            w_cut_fac = 4.0                                                    # :43-45
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("pyrmt_amd needs a visible MI355X")
+        from .bc import Disc
+        self.torch, self.N, self.scheme, self.mu_s = torch, int(N), scheme, float(mu_s)
+        self.w_cut_fac, self.detg_clamp, self.isochoric = w_cut_fac, detg_clamp, bool(isochoric)
+        dx, dy = mac_grid(N, N)
+        rho = self.RHO
+        self.dx, self.dy, self.w_t, self.nu = dx, dy, 2.0 * dx, self.MU_F / rho
+        self.disc = Disc(self.X0, self.Y0, self.R)
+        cs = np.sqrt(mu_s / rho)
+        self.cs2 = float(cs * cs) if self.use_elastic else 0.0                 # :113
+        self.dt = float(self.default_dt(N, name, mu_s) if dt is None else dt)
+        xc = (np.arange(N) + 0.5) * dx
+        Xc, Yc = np.meshgrid(xc, xc)
+        Xg, Yg = np.meshgrid(np.arange(N) * dx, np.arange(N) * dy)
+        phi = self.disc(Xc, Yc)
+        m = (phi <= 0).astype(float)
+        X1, X2 = extrapolate_reference_map(Xc * m, Yc * m, phi, dx, dy, self.LAYERS)   # :51
+        dev = lambda h: torch.from_numpy(np.ascontiguousarray(h, dtype=np.float64)).cuda()
+        self.Xg, self.Yg, self.X1, self.X2 = map(dev, (Xg, Yg, X1, X2))
+        self.u, self.v = dev(np.zeros((N, N + 1))), dev(np.zeros((N + 1, N)))
+        self.lx, self.ly = _axis_eigs(poisson_eigs_neumann(N, N, dx, dy))
+        self.ctx = ctx_for(N, N)
+        self.stats = torch.empty(8, dtype=torch.float64, device="cuda")
+        self.t, self.nsteps, self.diverged, self.record = 0.0, 0, False, []
+        self.sl_steps, self.pcg_iters = 0, (0, 0)
+        self.phi = self.J = None
+
+    @staticmethod
+    def parse_integrator(integrator=None, imex=False):
+        """:57-62 (host): the "-sl" suffix, then the ladder: (canonical name with its suffix,
+        use_semilag, use_imex, use_elastic)."""
+        istr = str(integrator).lower().replace("_", "-") if integrator is not None else ""
+        use_semilag = istr.endswith("-sl")
+        base = (istr[:-3] or "imex") if use_semilag else integrator
+        name, use_imex, use_elastic = resolve_integrator(base, imex=imex, supports_elastic=True)
+        if use_semilag:
+            use_imex = True; name = name + "-sl"
+        return name, use_semilag, use_imex, use_elastic
+
+    @classmethod
+    def default_dt(cls, N, integrator, mu_s=0.1):
+        """:63-74 for a canonical integrator name ("explicit", "imex", "imex-elastic", each with
+        an optional "-sl")."""
+        dx = 1.0 / N
+        sl = integrator.endswith("-sl")
+        _, use_imex, use_elastic = resolve_integrator(integrator[:-3] if sl else integrator)
+        cs = np.sqrt(mu_s / cls.RHO)
+        dt_adv = 0.3 * dx / cls.U_LID; dt_visc = 0.2 * dx * dx / (cls.MU_F / cls.RHO)
+        dt_elastic = 0.3 * dx / (cs + 1e-9)
+        if sl and use_elastic:
+            return 2.0 * dt_adv
+        if sl:
+            return min(2.0 * dt_adv, dt_elastic)
+        if use_elastic:
+            return dt_adv
+        if use_imex:
+            return min(dt_adv, dt_elastic)
+        return min(dt_adv, dt_visc, dt_elastic)
+
+    def _advect_maps(self, a, b, phi):
+        """:96-98 / :135-137: both components advected with the centre velocity (a, b), masked
+        with (phi <= 0), extrapolated."""
+        from . import functions as F
+        torch, dx, dy, dt, wc = self.torch, self.dx, self.dy, self.dt, self.w_cut_fac * self.dx
+        if self.scheme == "semilagrangian":
+            outs = [torch.empty_like(self.X1), torch.empty_like(self.X2)]
+            F._advect_sl_rk4_multi(self.ctx, [self.X1, self.X2], a, b, self.Xg, self.Yg, dt, dx,
+                                   dy, phi, outs)
+        else:
+            sm = (phi <= 0).to(torch.float64)
+            if self.scheme == "semilagrangian_cubic":
+                adv = lambda q: F.advect_semilagrangian_cubic_rk4(q, a, b, self.Xg, self.Yg, dt,
+                                                                  dx, dy)
+            elif self.scheme == "central2":
+                adv = lambda q: F.advect_central2_rk3(q, a, b, dx, dy, dt, phi, wc)
+            else:
+                adv = lambda q: F.advect_weno5_rk3(q, a, b, dx, dy, dt, phi, wc)
+            outs = [adv(self.X1) * sm, adv(self.X2) * sm]
+        self.X1, self.X2 = extrapolate_reference_map(outs[0], outs[1], phi, dx, dy, self.LAYERS)
+
+    def step(self, nsteps=1, t_end=math.inf):
+        from .functions import rebuild_phi_from_reference_map
+        torch, dx, dy, dt, rho = self.torch, self.dx, self.dy, self.dt, self.RHO
+        for _ in range(int(nsteps)):
+            if self.diverged or not self.t < t_end:
+                break
+            u, v = self.u, self.v
+            phi = rebuild_phi_from_reference_map(self.X1, self.X2, self.disc)      # :84
+            if not self.use_elastic:
+                u_c, v_c = midpoint_centres(u, v, u, v)                            # :82-83
+                self._advect_maps(u_c, v_c, phi)
+                phi = rebuild_phi_from_reference_map(self.X1, self.X2, self.disc)  # :99
+            fu, fv, J = solid_force(self.X1, self.X2, phi, dx, dy, self.w_t, self.mu_s,
+                                    self.KAPPA, self.detg_clamp, self.isochoric)
+            took_sl, its = False, (0, 0)
+            if self.use_semilag:                                                   # :114-127
+                ustar, vstar, its, took_sl = _predictor_lid_semilag(
+                    u, v, self.nu, dx, dy, dt, self.U_LID, fu, fv, rho, self.cs2, 1e-8, 0.9)
+            elif self.use_imex:
+                ustar, vstar, its = _predictor_lid_imex(u, v, self.nu, dx, dy, dt, self.U_LID, fu,
+                                                        fv, rho, 1e-8, self.cs2)
+            else:
+                ustar, vstar = momentum_predictor(u, v, self.nu, dx, dy, dt, self.U_LID, fu=fu,
+                                                  fv=fv, rho=rho)
+            # project(), the symbol's axes split once at set-up (not per step)
+            un, vn, p = torch.empty_like(u), torch.empty_like(v), torch.empty_like(phi)
+            L.check(L.lib().rmt_mac_project(self.ctx.bind(), _p(ustar), _p(vstar), dx, dy, dt,
+                                            float(rho), _hp(self.lx), _hp(self.ly), _p(un),
+                                            _p(vn), _p(p)), "project")
+            if self.use_elastic:                                                   # :130-137
+                umc, vmc = midpoint_centres(u, v, un, vn)
+                self._advect_maps(umc, vmc, phi)
+            self.u, self.v, self.phi, self.J = un, vn, phi, J
+            self.pcg_iters = tuple(its)
+            soft_diag(phi, J, un, vn, dx, dy, out=self.stats)
+            count, sx, sy, minJ, maxJ, _, _, bad = self.stats.tolist()  # the step's host read
+            if count == 0 or bad or minJ < 0.0 or maxJ > 20.0:                     # :139-147
+                self.diverged = True
+                break
+            self.t += dt
+            self.nsteps += 1
+            self.sl_steps += int(took_sl)
+            self.record.append((self.t, sx / count, sy / count, minJ, maxJ))
+        return self
+
+    def state(self):
+        """Host copies of u, v, X1, X2, and t."""
+        g = lambda t: t.cpu().numpy()
+        return dict(u=g(self.u), v=g(self.v), X1=g(self.X1), X2=g(self.X2), t=self.t)
+
+    def set_state(self, state):
+        """The fields of state() (arrays or device tensors; any subset)."""
+        unknown = set(state) - set(self.STATE)
+        if unknown:
+            raise KeyError(f"set_state: unknown fields {sorted(unknown)}; one of {self.STATE}")
+        N, io = self.N, _IO(None)
+        shapes = {"u": (N, N + 1), "v": (N + 1, N)}
+        for k, val in state.items():
+            if k == "t":
+                self.t = float(val)
+                continue
+            if tuple(np.shape(val)) != shapes.get(k, (N, N)):
+                raise ValueError(f"set_state: {k} has shape {tuple(np.shape(val))}")
+            setattr(self, k, io.dev(val).clone())
+        self.diverged = False
+
+    def get(self, name):
+        return getattr(self, name).cpu().numpy()
+
+
+def mac_soft_disc_run(N=128, t_end=8.0, scheme="semilagrangian", w_cut_fac=0.0, detg_clamp=0.0,
+                      reinit=False, isochoric=False, imex=False, dt=None, integrator=None,
+                      mu_s=0.1, return_sim=False):
+    """mac_soft_disc_lid.py:23-157 (run(..., write=False)): integrate to t_end or to the
+    `diverged` stop; returns the (n, 5) trajectory (t, cx, cy, min J, max J) (return_sim:
+    (trajectory, the MacSoftDisc))."""
+    if not math.isfinite(t_end):
+        raise ValueError("mac_soft_disc_run: a finite t_end")
+    sim = MacSoftDisc(N, integrator=integrator, imex=imex, dt=dt, mu_s=mu_s, scheme=scheme,
+                      w_cut_fac=w_cut_fac, detg_clamp=detg_clamp, isochoric=isochoric,
+                      reinit=reinit)
+    sim.step(2**31 - 1, t_end)
+    traj = np.array(sim.record)
+    return (traj, sim) if return_sim else traj
