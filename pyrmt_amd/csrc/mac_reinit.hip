@@ -110,19 +110,12 @@ __global__ void __launch_bounds__(256) k_mac_total_stress(const double *__restri
 }
 
 // ---------------------------------------------------------- fused face forces ----
-// A workgroup owns the 64 x 16 cells of a tile, the x-faces left of them and the y-faces below
-// them (the last tile column / row also the wall faces nx / ny, zero like face 0).  A face
-// averages the divergence of its two cells, the divergence reaches S one cell further (two
-// inwards at a grid edge) and S reaches xi one more: S on the tile + 2 left / below and + 1
-// right / above, xi on + 3 and + 2, both clipped to the grid.  At a grid edge the one-sided
-// stencils read two cells inwards, which the clipped regions hold whatever the width of the
-// last tile (nx, ny >= 5).  LDS: 2 x 69 x 21 + 3 x 67 x 19 doubles = 52.5 KiB, three
-// workgroups a CU.
-constexpr int MR_TX = 64, MR_TY = 16, MR_T = 256;
-constexpr int MR_XW = MR_TX + 5, MR_XH = MR_TY + 5;
-constexpr int MR_SW = MR_TX + 3, MR_SH = MR_TY + 3;
+// The face-force tile of rmt_internal.hpp with the map staged in LDS: S reaches xi one cell
+// further, so xi lies on the tile + 3 left / below and + 2 right / above, clipped to the grid.
+// LDS: 2 x 69 x 21 + 3 x 67 x 19 doubles = 52.5 KiB, three workgroups a CU.
+constexpr int MR_XW = FF_TX + 5, MR_XH = FF_TY + 5;
 
-__global__ void __launch_bounds__(MR_T) k_mac_total_force(const double *__restrict__ X1,
+__global__ void __launch_bounds__(FF_T) k_mac_total_force(const double *__restrict__ X1,
                                                           const double *__restrict__ X2, MrFs Fs,
                                                           const double *__restrict__ phi, int ny,
                                                           int nx, double h2x, double h2y,
@@ -131,69 +124,36 @@ __global__ void __launch_bounds__(MR_T) k_mac_total_force(const double *__restri
                                                           double *__restrict__ fv,
                                                           double *__restrict__ Jep) {
     __shared__ double sx1[MR_XH * MR_XW], sx2[MR_XH * MR_XW];
-    __shared__ double sxx[MR_SH * MR_SW], sxy[MR_SH * MR_SW], syy[MR_SH * MR_SW];
-    const int i0 = blockIdx.x * MR_TX, j0 = blockIdx.y * MR_TY, tid = threadIdx.x;
+    __shared__ double sxx[FF_SH * FF_SW], sxy[FF_SH * FF_SW], syy[FF_SH * FF_SW];
+    const int i0 = blockIdx.x * FF_TX, j0 = blockIdx.y * FF_TY, tid = threadIdx.x;
     // xi: columns [xa, xb], rows [ya, yb]
-    const int xa = max(0, i0 - 3), xb = min(nx - 1, i0 + MR_TX + 1);
-    const int ya = max(0, j0 - 3), yb = min(ny - 1, j0 + MR_TY + 1);
+    const int xa = max(0, i0 - 3), xb = min(nx - 1, i0 + FF_TX + 1);
+    const int ya = max(0, j0 - 3), yb = min(ny - 1, j0 + FF_TY + 1);
     const int xw = xb - xa + 1, xn = xw * (yb - ya + 1);
-    for (int q = tid; q < xn; q += MR_T) {
+    for (int q = tid; q < xn; q += FF_T) {
         const int r = q / xw, cc = q - r * xw;
         const long g = (long)(ya + r) * nx + xa + cc;
         sx1[r * MR_XW + cc] = X1[g];
         sx2[r * MR_XW + cc] = X2[g];
     }
     __syncthreads();
-    // S: columns [sa, sb], rows [ta, tb]
-    const int sa = max(0, i0 - 2), sb = min(nx - 1, i0 + MR_TX);
-    const int ta = max(0, j0 - 2), tb = min(ny - 1, j0 + MR_TY);
-    const int sw = sb - sa + 1, sn = sw * (tb - ta + 1);
-    for (int q = tid; q < sn; q += MR_T) {
-        const int r = q / sw, cc = q - r * sw;
-        const int i = sa + cc, j = ta + r;
-        const long g = (long)j * nx + i;
+    ff_stress_region(i0, j0, nx, ny, [&](int i, int j, long g, int s, bool owned) {
         const int l = (j - ya) * MR_XW + (i - xa);
         TotCell o;
         total_stress_cell(sx1 + l, sx2 + l, MR_XW, i, j, nx, ny, h2x, h2y, Fs.p[0][g], Fs.p[1][g],
                           Fs.p[2][g], Fs.p[3][g], phi[g], w_t, mu_s, o);
-        sxx[r * MR_SW + cc] = o.S[0]; sxy[r * MR_SW + cc] = o.S[1]; syy[r * MR_SW + cc] = o.S[2];
-        if (i >= i0 && i < i0 + MR_TX && j >= j0 && j < j0 + MR_TY) Jep[g] = o.J;
-    }
+        sxx[s] = o.S[0]; sxy[s] = o.S[1]; syy[s] = o.S[2];
+        if (owned) Jep[g] = o.J;
+    });
     __syncthreads();
-    // :82-85 on the owned faces: div at a cell from the S tile, 0.5 * (div + div of the cell
-    // before)
-    for (int q = tid; q < MR_TX * MR_TY; q += MR_T) {
-        const int lj = q / MR_TX, li = q - lj * MR_TX;
-        const int i = i0 + li, j = j0 + lj;
-        if (i >= nx || j >= ny) continue;
-        const int l = (j - ta) * MR_SW + (i - sa);
-        double u = 0.0, v = 0.0;
-        if (i > 0) {
-            const double d1 = grad2(sxx + l, 1, i, nx, h2x) + grad2(sxy + l, MR_SW, j, ny, h2y);
-            const double d0 = grad2(sxx + l - 1, 1, i - 1, nx, h2x) +
-                              grad2(sxy + l - 1, MR_SW, j, ny, h2y);
-            u = 0.5 * (d1 + d0);
-        }
-        if (j > 0) {
-            const double d1 = grad2(sxy + l, 1, i, nx, h2x) + grad2(syy + l, MR_SW, j, ny, h2y);
-            const double d0 = grad2(sxy + l - MR_SW, 1, i, nx, h2x) +
-                              grad2(syy + l - MR_SW, MR_SW, j - 1, ny, h2y);
-            v = 0.5 * (d1 + d0);
-        }
-        fu[(long)j * (nx + 1) + i] = u;
-        fv[(long)j * nx + i] = v;
-        if (i == nx - 1) fu[(long)j * (nx + 1) + nx] = 0.0;
-        if (j == ny - 1) fv[(long)ny * nx + i] = 0.0;
-    }
+    ff_faces(sxx, sxy, syy, i0, j0, nx, ny, h2x, h2y, fu, fv);                     // :82-85
 }
 
 // -------------------------------------------------------------- epoch distortion ----
 // max J, min J (NaN propagates, as ndarray.max / min) and the count over phi <= 0: order-free,
-// so exact.  MR_RB workgroups leave partials in ctx->red, one workgroup folds them.
-constexpr int MR_RB = 256;
-__device__ __forceinline__ double mr_nanmin(double a, double b) {
-    return (a != a || b != b) ? (a + b) : (a < b ? a : b);
-}
+// so exact.  MR_RB workgroups of MR_T threads leave partials in ctx->red, one workgroup folds
+// them.
+constexpr int MR_RB = 256, MR_T = 256;
 __device__ __forceinline__ void mr_fold(double *smx, double *smn, double *sct, double &mx,
                                         double &mn, double &ct) {
     const int t = threadIdx.x;
@@ -201,7 +161,7 @@ __device__ __forceinline__ void mr_fold(double *smx, double *smn, double *sct, d
     __syncthreads();
     tree_fold<MR_T>([&](int t, int u) {
         smx[t] = nanmax(smx[t], smx[u]);
-        smn[t] = mr_nanmin(smn[t], smn[u]);
+        smn[t] = nanmin(smn[t], smn[u]);
         sct[t] = sct[t] + sct[u];
     });
     mx = smx[0]; mn = smn[0]; ct = sct[0];
@@ -213,7 +173,7 @@ __global__ void __launch_bounds__(MR_T) k_mac_epoch_p1(const double *__restrict_
     double mx = -INFINITY, mn = INFINITY, ct = 0.0;
     for (long k = blockIdx.x * (long)MR_T + threadIdx.x; k < n; k += (long)MR_RB * MR_T)
         if (phi[k] <= 0.0) {
-            mx = nanmax(mx, J[k]); mn = mr_nanmin(mn, J[k]); ct += 1.0;
+            mx = nanmax(mx, J[k]); mn = nanmin(mn, J[k]); ct += 1.0;
         }
     mr_fold(smx, smn, sct, mx, mn, ct);
     if (threadIdx.x == 0) {
@@ -232,8 +192,6 @@ static_assert(3 * MR_RB <= RED_BLOCKS + 64, "ctx->red holds the partials");
 
 }  // namespace rmt
 using namespace rmt;
-
-#define N_CELLS ((long)ctx->ny * ctx->nx)
 
 template <int NP>
 static void launch_multi(rmt_ctx *ctx, const MrPlanes &P, const double *a, const double *b,
@@ -298,8 +256,8 @@ int rmt_mac_total_force(rmt_ctx *ctx, const double *X1, const double *X2,
     RMT_CHECK(ctx && X1 && X2 && phi && fu && fv && J_ep, RMT_EINVAL, "null argument");
     MrFs F;
     RMT_TRY(mr_fs(Fs, F));
-    const dim3 grid((ctx->nx + MR_TX - 1) / MR_TX, (ctx->ny + MR_TY - 1) / MR_TY);
-    k_mac_total_force<<<grid, MR_T, 0, ctx->stream>>>(X1, X2, F, phi, ctx->ny, ctx->nx, 2 * dx,
+    const dim3 grid((ctx->nx + FF_TX - 1) / FF_TX, (ctx->ny + FF_TY - 1) / FF_TY);
+    k_mac_total_force<<<grid, FF_T, 0, ctx->stream>>>(X1, X2, F, phi, ctx->ny, ctx->nx, 2 * dx,
                                                       2 * dy, w_t, mu_s, fu, fv, J_ep);
     RMT_LAUNCHED();
     return RMT_OK;

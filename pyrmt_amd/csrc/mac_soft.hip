@@ -15,17 +15,10 @@
 namespace rmt {
 
 // ------------------------------------------------------------ fused face forces ----
-// The tiling of k_mac_total_force (mac_reinit.hip): a workgroup owns 64 x 16 cells, the x-faces
-// left of them and the y-faces below them (the last tile column / row also the wall faces).
-// The blended stress is needed on the tile + 2 left / below and + 1 right / above, clipped to
-// the grid; at a grid edge the one-sided stencils read two cells inwards, which the clipped
-// region holds (nx, ny >= 5).  The map and phi are read from global memory through
+// The face-force tile of rmt_internal.hpp.  The map and phi are read from global memory through
 // solid_stress_cell, the operator's own cell function: outside phi <= 0 it returns after one
 // load.  LDS: 3 x 67 x 19 doubles = 29.8 KiB.
-constexpr int MS_TX = 64, MS_TY = 16, MS_T = 256;
-constexpr int MS_SW = MS_TX + 3, MS_SH = MS_TY + 3;
-
-__global__ void __launch_bounds__(MS_T) k_mac_solid_force(const double *__restrict__ X1,
+__global__ void __launch_bounds__(FF_T) k_mac_solid_force(const double *__restrict__ X1,
                                                           const double *__restrict__ X2,
                                                           const double *__restrict__ phi, int ny,
                                                           int nx, double dx, double dy, double w_t,
@@ -33,51 +26,19 @@ __global__ void __launch_bounds__(MS_T) k_mac_solid_force(const double *__restri
                                                           int iso, double *__restrict__ fu,
                                                           double *__restrict__ fv,
                                                           double *__restrict__ J) {
-    __shared__ double sxx[MS_SH * MS_SW], sxy[MS_SH * MS_SW], syy[MS_SH * MS_SW];
-    const int i0 = blockIdx.x * MS_TX, j0 = blockIdx.y * MS_TY, tid = threadIdx.x;
+    __shared__ double sxx[FF_SH * FF_SW], sxy[FF_SH * FF_SW], syy[FF_SH * FF_SW];
+    const int i0 = blockIdx.x * FF_TX, j0 = blockIdx.y * FF_TY;
     const double h2x = 2 * dx, h2y = 2 * dy;
-    // S: columns [sa, sb], rows [ta, tb]
-    const int sa = max(0, i0 - 2), sb = min(nx - 1, i0 + MS_TX);
-    const int ta = max(0, j0 - 2), tb = min(ny - 1, j0 + MS_TY);
-    const int sw = sb - sa + 1, sn = sw * (tb - ta + 1);
-    for (int q = tid; q < sn; q += MS_T) {
-        const int r = q / sw, cc = q - r * sw;
-        const int i = sa + cc, j = ta + r;
-        const long g = (long)j * nx + i;
+    ff_stress_region(i0, j0, nx, ny, [&](int i, int j, long g, int l, bool owned) {
         Stress s{0.0, 0.0, 0.0, 1.0};
         if (j >= 1 && j < ny - 1 && i >= 1 && i < nx - 1)
             solid_stress_cell(X1, X2, phi, g, nx, dx, dy, mu_s, kappa, 0.0, clamp, iso != 0, s);
         const double b = 1 - heaviside(phi[g], w_t);
-        sxx[r * MS_SW + cc] = b * s.sxx; sxy[r * MS_SW + cc] = b * s.sxy;
-        syy[r * MS_SW + cc] = b * s.syy;
-        if (i >= i0 && i < i0 + MS_TX && j >= j0 && j < j0 + MS_TY) J[g] = s.J;
-    }
+        sxx[l] = b * s.sxx; sxy[l] = b * s.sxy; syy[l] = b * s.syy;
+        if (owned) J[g] = s.J;
+    });
     __syncthreads();
-    // :107-110 on the owned faces: div at a cell from the S tile, 0.5 * (div + div of the cell
-    // before)
-    for (int q = tid; q < MS_TX * MS_TY; q += MS_T) {
-        const int lj = q / MS_TX, li = q - lj * MS_TX;
-        const int i = i0 + li, j = j0 + lj;
-        if (i >= nx || j >= ny) continue;
-        const int l = (j - ta) * MS_SW + (i - sa);
-        double u = 0.0, v = 0.0;
-        if (i > 0) {
-            const double d1 = grad2(sxx + l, 1, i, nx, h2x) + grad2(sxy + l, MS_SW, j, ny, h2y);
-            const double d0 = grad2(sxx + l - 1, 1, i - 1, nx, h2x) +
-                              grad2(sxy + l - 1, MS_SW, j, ny, h2y);
-            u = 0.5 * (d1 + d0);
-        }
-        if (j > 0) {
-            const double d1 = grad2(sxy + l, 1, i, nx, h2x) + grad2(syy + l, MS_SW, j, ny, h2y);
-            const double d0 = grad2(sxy + l - MS_SW, 1, i, nx, h2x) +
-                              grad2(syy + l - MS_SW, MS_SW, j - 1, ny, h2y);
-            v = 0.5 * (d1 + d0);
-        }
-        fu[(long)j * (nx + 1) + i] = u;
-        fv[(long)j * nx + i] = v;
-        if (i == nx - 1) fu[(long)j * (nx + 1) + nx] = 0.0;
-        if (j == ny - 1) fv[(long)ny * nx + i] = 0.0;
-    }
+    ff_faces(sxx, sxy, syy, i0, j0, nx, ny, h2x, h2y, fu, fv);                     // :107-110
 }
 
 // ------------------------------------------------------------- midpoint centres ----
@@ -101,20 +62,17 @@ __global__ void __launch_bounds__(256) k_mac_midpoint_centres(const double *__re
 // ------------------------------------------------------------------ diagnostics ----
 // out8: the count of phi <= 0, the sums of Xc and Yc over them (Xc = (i + 0.5) dx as the
 // driver's meshgrid), min J, max J (NaN propagates, as ndarray.min / max), max|u|, max|v| (the
-// same) and 1.0 if u or v holds a non-finite value.  MS_RB workgroups leave partials in
-// ctx->red, one workgroup folds them: a fixed order, so the sums repeat bit for bit.
-constexpr int MS_RB = 128, MS_NQ = 8;
+// same) and 1.0 if u or v holds a non-finite value.  MS_RB workgroups of MS_T threads leave
+// partials in ctx->red, one workgroup folds them: a fixed order, so the sums repeat bit for bit.
+constexpr int MS_RB = 128, MS_T = 256, MS_NQ = 8;
 static_assert(MS_NQ * MS_RB <= RED_BLOCKS + 64, "ctx->red holds the partials");
 struct SoftAcc { double q[MS_NQ]; };
 __device__ __forceinline__ SoftAcc soft_identity() {
     return {{0.0, 0.0, 0.0, INFINITY, -INFINITY, 0.0, 0.0, 0.0}};
 }
-__device__ __forceinline__ double ms_nanmin(double a, double b) {
-    return (a != a || b != b) ? (a + b) : (a < b ? a : b);
-}
 __device__ __forceinline__ void soft_merge(SoftAcc &a, const SoftAcc &b) {
     a.q[0] = a.q[0] + b.q[0]; a.q[1] = a.q[1] + b.q[1]; a.q[2] = a.q[2] + b.q[2];
-    a.q[3] = ms_nanmin(a.q[3], b.q[3]); a.q[4] = nanmax(a.q[4], b.q[4]);
+    a.q[3] = nanmin(a.q[3], b.q[3]); a.q[4] = nanmax(a.q[4], b.q[4]);
     a.q[5] = nanmax(a.q[5], b.q[5]); a.q[6] = nanmax(a.q[6], b.q[6]);
     a.q[7] = nanmax(a.q[7], b.q[7]);
 }
@@ -135,7 +93,7 @@ __global__ void __launch_bounds__(MS_T) k_mac_soft_diag_p1(const double *__restr
     const long stride = (long)MS_RB * MS_T, first = blockIdx.x * (long)MS_T + threadIdx.x;
     const long n = (long)ny * nx, nu = (long)ny * (nx + 1), nv = (long)(ny + 1) * nx;
     for (long k = first; k < n; k += stride) {
-        a.q[3] = ms_nanmin(a.q[3], J[k]); a.q[4] = nanmax(a.q[4], J[k]);
+        a.q[3] = nanmin(a.q[3], J[k]); a.q[4] = nanmax(a.q[4], J[k]);
         if (phi[k] <= 0.0) {
             const int j = (int)(k / nx), i = (int)(k % nx);
             a.q[0] += 1.0; a.q[1] += (i + 0.5) * dx; a.q[2] += (j + 0.5) * dy;
@@ -198,14 +156,12 @@ __global__ void __launch_bounds__(256) k_mac_xi_cons_stage(const double *__restr
 }  // namespace rmt
 using namespace rmt;
 
-#define N_CELLS ((long)ctx->ny * ctx->nx)
-
 int rmt_mac_solid_force(rmt_ctx *ctx, const double *X1, const double *X2, const double *phi,
                         double dx, double dy, double w_t, double mu_s, double kappa,
                         double detg_clamp, int isochoric, double *fu, double *fv, double *J) {
     RMT_CHECK(ctx && X1 && X2 && phi && fu && fv && J, RMT_EINVAL, "null argument");
-    const dim3 grid((ctx->nx + MS_TX - 1) / MS_TX, (ctx->ny + MS_TY - 1) / MS_TY);
-    k_mac_solid_force<<<grid, MS_T, 0, ctx->stream>>>(X1, X2, phi, ctx->ny, ctx->nx, dx, dy, w_t,
+    const dim3 grid((ctx->nx + FF_TX - 1) / FF_TX, (ctx->ny + FF_TY - 1) / FF_TY);
+    k_mac_solid_force<<<grid, FF_T, 0, ctx->stream>>>(X1, X2, phi, ctx->ny, ctx->nx, dx, dy, w_t,
                                                       mu_s, kappa, detg_clamp, isochoric, fu, fv,
                                                       J);
     RMT_LAUNCHED();

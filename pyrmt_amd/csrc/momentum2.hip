@@ -21,11 +21,6 @@ constexpr int M2_TX = 64, M2_TY = 16, M2_T = 256;
 constexpr int M2_UX = M2_TX + 6, M2_UY = M2_TY + 6;   // outer plane
 constexpr int M2_GX = M2_TX + 4, M2_GY = M2_TY + 4;   // derived plane
 
-// NaN-propagating minimum (np.minimum)
-__device__ __forceinline__ double nanmin(double a, double b) {
-    return (a != a || b != b) ? (a + b) : (a < b ? a : b);
-}
-
 // ------------------------------------------------------------------ curvature ----
 // functions.py:837-861: n = grad(phi) / (sqrt(phi_x^2 + phi_y^2) + 1e-12), kappa = d_x n_x +
 // d_y n_y, every derivative grad_central_*_2nd.  phi on the tile + 3, n on the tile + 2.
@@ -101,7 +96,7 @@ __global__ void k_st_force(const double *__restrict__ H, const double *__restric
     fy[c] = g * grad2(H + c, nx, j, ny, 2 * dy);
 }
 
-// (o may be a)
+// np.minimum (o may be a)
 __global__ void k_nanmin(const double *a, const double *__restrict__ b, long n, double *o) {
     const long c = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (c < n) o[c] = nanmin(a[c], b[c]);

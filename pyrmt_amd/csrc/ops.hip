@@ -875,7 +875,6 @@ int rmt_ctx_destroy(rmt_ctx *ctx) {
     return RMT_OK;
 }
 
-#define N_CELLS ((long)ctx->ny * ctx->nx)
 #define LAUNCH1D(n) grid1d((n), 256), 256, 0, ctx->stream
 
 int rmt_grad_x_2nd(rmt_ctx *ctx, const double *f, double h, double *out) {

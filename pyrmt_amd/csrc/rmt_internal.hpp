@@ -30,6 +30,10 @@ inline unsigned list_grid(long max_tiles) {
 __host__ __device__ __forceinline__ double nanmax(double a, double b) {
     return (a != a || b != b) ? (a + b) : (a > b ? a : b);
 }
+// NaN-propagating min (np.minimum, ndarray.min)
+__host__ __device__ __forceinline__ double nanmin(double a, double b) {
+    return (a != a || b != b) ? (a + b) : (a < b ? a : b);
+}
 // The other NaN-propagating max, folding y into x: it selects an operand and does no
 // arithmetic, so a NaN comes out with its own bits (nanmax's a + b makes a new quiet one) and
 // x stays on a tie (+-0 included).  Both are exact in any order; each reduction keeps the
@@ -216,6 +220,7 @@ struct StreamScope {
 int ensure_scratch(rmt_ctx *ctx, size_t bytes);    // >= bytes of double scratch
 int ensure_bytes(rmt_ctx *ctx, size_t bytes);      // >= bytes of byte scratch
 inline unsigned grid1d(long n, int block) { return (unsigned)((n + block - 1) / block); }
+#define N_CELLS ((long)ctx->ny * ctx->nx)          // of the `ctx` in scope
 
 // A launch whose completion also completes `done` (hipExtLaunchKernel's stop event tracks the
 // kernel itself: no marker packet between it and the stream's next launch -- an event record
@@ -507,6 +512,65 @@ __device__ __forceinline__ bool solid_stress_cell(const double *__restrict__ X1,
     return solid_stress_acc([&](int o) { return X1[off[o]]; }, [&](int o) { return X2[off[o]]; },
                             [&](int o) { return phi[off[o]]; }, dx, dy, mu_s, kappa, w_cut,
                             clamp, iso, out);
+}
+
+// ------------------------------------------------------------- face-force tile --
+// The tile of the fused face-force kernels (k_mac_total_force, k_mac_solid_force).  A workgroup
+// of FF_T threads owns the FF_TX x FF_TY cells from (i0, j0), the x-faces left of them and the
+// y-faces below them (the last tile column / row also the wall faces nx / ny, zero like face
+// 0).  A face averages the divergence of its two cells and the divergence reaches the stress S
+// one cell further (two inwards at a grid edge): S on the tile + 2 left / below and + 1 right /
+// above, clipped to the grid, in three LDS planes of FF_SH rows of FF_SW.  At a grid edge the
+// one-sided stencils read two cells inwards, which the clipped region holds whatever the width
+// of the last tile (nx, ny >= 5).
+constexpr int FF_TX = 64, FF_TY = 16, FF_T = 256;
+constexpr int FF_SW = FF_TX + 3, FF_SH = FF_TY + 3;
+
+// The S region, columns [sa, sb] and rows [ta, tb]: cell(i, j, g, l, owned) once for each of
+// its cells, g the cell in the global plane, l its slot in an S plane, owned: a cell of the
+// tile itself.  The caller synchronises before ff_faces.
+template <class Cell>
+__device__ __forceinline__ void ff_stress_region(int i0, int j0, int nx, int ny, Cell cell) {
+    const int sa = max(0, i0 - 2), sb = min(nx - 1, i0 + FF_TX);
+    const int ta = max(0, j0 - 2), tb = min(ny - 1, j0 + FF_TY);
+    const int sw = sb - sa + 1, sn = sw * (tb - ta + 1);
+    for (int q = threadIdx.x; q < sn; q += FF_T) {
+        const int r = q / sw, cc = q - r * sw;
+        const int i = sa + cc, j = ta + r;
+        cell(i, j, (long)j * nx + i, r * FF_SW + cc,
+             i >= i0 && i < i0 + FF_TX && j >= j0 && j < j0 + FF_TY);
+    }
+}
+
+// The owned faces from the S planes: div at a cell, 0.5 * (div + div of the cell before);
+// h2x = 2 dx, h2y = 2 dy.
+__device__ __forceinline__ void ff_faces(const double *sxx, const double *sxy, const double *syy,
+                                         int i0, int j0, int nx, int ny, double h2x, double h2y,
+                                         double *__restrict__ fu, double *__restrict__ fv) {
+    const int sa = max(0, i0 - 2), ta = max(0, j0 - 2);
+    for (int q = threadIdx.x; q < FF_TX * FF_TY; q += FF_T) {
+        const int lj = q / FF_TX, li = q - lj * FF_TX;
+        const int i = i0 + li, j = j0 + lj;
+        if (i >= nx || j >= ny) continue;
+        const int l = (j - ta) * FF_SW + (i - sa);
+        double u = 0.0, v = 0.0;
+        if (i > 0) {
+            const double d1 = grad2(sxx + l, 1, i, nx, h2x) + grad2(sxy + l, FF_SW, j, ny, h2y);
+            const double d0 = grad2(sxx + l - 1, 1, i - 1, nx, h2x) +
+                              grad2(sxy + l - 1, FF_SW, j, ny, h2y);
+            u = 0.5 * (d1 + d0);
+        }
+        if (j > 0) {
+            const double d1 = grad2(sxy + l, 1, i, nx, h2x) + grad2(syy + l, FF_SW, j, ny, h2y);
+            const double d0 = grad2(sxy + l - FF_SW, 1, i, nx, h2x) +
+                              grad2(syy + l - FF_SW, FF_SW, j - 1, ny, h2y);
+            v = 0.5 * (d1 + d0);
+        }
+        fu[(long)j * (nx + 1) + i] = u;
+        fv[(long)j * nx + i] = v;
+        if (i == nx - 1) fu[(long)j * (nx + 1) + nx] = 0.0;
+        if (j == ny - 1) fv[(long)ny * nx + i] = 0.0;
+    }
 }
 
 // functions.py:256-318 WENO5 reconstructions (Jiang-Shu, eps 1e-6; x**2 as x*x like Numba).

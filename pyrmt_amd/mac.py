@@ -20,6 +20,7 @@ mac_reinit.hip): ``total_stress``, ``total_force``, ``epoch_distortion`` and the
 The soft disc under the integrator ladder (benchmarks/mac_soft_disc_lid.py, mac.py:43-78,
 698-721, mac_soft.hip): ``resolve_integrator``, ``solid_force``, ``midpoint_centres``,
 ``soft_diag``, ``advect_xi_conservative`` and the loop ``MacSoftDisc`` / ``mac_soft_disc_run``.
+Both loops stand on ``_LidDisc`` (the disc, the set-up, the projection, the state).
 """
 import ctypes
 import math
@@ -962,6 +963,101 @@ class MacTwoDiscContact(MacMultiDisc):
         return np.column_stack([d["t"], cx[:, 0], cx[:, 1], cx[:, 1] - cx[:, 0]])
 
 
+# ------------------------------------------------------------------ lid-cavity disc loops --
+class _LidDisc:
+    """What the operator-composed loops of one soft disc (R 0.2 at (0.6, 0.5)) in the lid cavity
+    share: the disc, the set-up, the projection with the symbol's axes split once, and the
+    state.  A subclass names its state() fields in STATE and in KINDS those that are not a
+    (N, N) cell plane: "uface" / "vface" the face shapes, "planes4" a list of four cell planes
+    (one (4, N, N) array in state()), float / int a host scalar.  Each keeps its own step()."""
+
+    X0, Y0, R, LAYERS = 0.6, 0.5, 0.2, 3
+    STATE = ("u", "v", "X1", "X2", "t")
+    KINDS = {"u": "uface", "v": "vface", "t": float}
+
+    def _setup(self, N, rho, mu_f):
+        """The grid, the disc's level set, the masked and extrapolated initial map, the fluid at
+        rest, the projection's per-axis symbol, the context and the bookkeeping; returns the
+        host (Xc, Yc, phi) of the cell centres."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("pyrmt_amd needs a visible MI355X")
+        from .bc import Disc
+        self.torch, self.N, self.rho = torch, int(N), rho
+        dx, dy = mac_grid(N, N)
+        self.dx, self.dy, self.w_t, self.nu = dx, dy, 2.0 * dx, mu_f / rho
+        self.disc = Disc(self.X0, self.Y0, self.R)
+        xc = (np.arange(N) + 0.5) * dx
+        Xc, Yc = np.meshgrid(xc, xc)
+        Xg, Yg = np.meshgrid(np.arange(N) * dx, np.arange(N) * dy)
+        phi = self.disc(Xc, Yc)
+        m = (phi <= 0).astype(float)
+        X1, X2 = extrapolate_reference_map(Xc * m, Yc * m, phi, dx, dy, self.LAYERS)
+        self.Xg, self.Yg, self.X1, self.X2 = map(self._dev, (Xg, Yg, X1, X2))
+        self.u, self.v = self._dev(np.zeros((N, N + 1))), self._dev(np.zeros((N + 1, N)))
+        self.lx, self.ly = _axis_eigs(poisson_eigs_neumann(N, N, dx, dy))
+        self.ctx = ctx_for(N, N)
+        self.t, self.nsteps, self.diverged, self.record = 0.0, 0, False, []
+        return Xc, Yc, phi
+
+    def _dev(self, h):
+        return self.torch.from_numpy(np.ascontiguousarray(h, dtype=np.float64)).cuda()
+
+    @staticmethod
+    def _dt_bounds(dx, U_lid, nu, mu_s, rho):
+        """The advective, viscous and elastic-wave bounds on dt."""
+        cs = np.sqrt(mu_s / rho)
+        return 0.3 * dx / U_lid, 0.2 * dx * dx / nu, 0.3 * dx / (cs + 1e-9)
+
+    def _project(self, ustar, vstar, dt):
+        """project() with the symbol's axes split once at set-up (not per step): (u, v, p)."""
+        u, v = self.torch.empty_like(ustar), self.torch.empty_like(vstar)
+        p = ustar.new_empty((self.N, self.N))
+        L.check(L.lib().rmt_mac_project(self.ctx.bind(), _p(ustar), _p(vstar), self.dx, self.dy,
+                                        dt, float(self.rho), _hp(self.lx), _hp(self.ly), _p(u),
+                                        _p(v), _p(p)), "project")
+        return u, v, p
+
+    def state(self):
+        """Host copies of the fields of STATE."""
+        g = lambda t: t.cpu().numpy()
+        out = {}
+        for k in self.STATE:
+            kind, val = self.KINDS.get(k), getattr(self, k)
+            out[k] = (val if kind in (float, int) else
+                      np.stack([g(p) for p in val]) if kind == "planes4" else g(val))
+        return out
+
+    def set_state(self, state):
+        """The fields of state() (arrays or device tensors; any subset)."""
+        unknown = set(state) - set(self.STATE)
+        if unknown:
+            raise KeyError(f"set_state: unknown fields {sorted(unknown)}; one of {self.STATE}")
+        N, io = self.N, _IO(None)
+        shapes = {"uface": (N, N + 1), "vface": (N + 1, N), "planes4": (4, N, N)}
+        for k, val in state.items():
+            kind = self.KINDS.get(k)
+            if kind in (float, int):
+                setattr(self, k, kind(val))
+                continue
+            if tuple(np.shape(val)) != shapes.get(kind, (N, N)):
+                raise ValueError(f"set_state: {k} has shape {tuple(np.shape(val))}")
+            d = io.dev(val).clone()
+            setattr(self, k, [d[i].contiguous() for i in range(4)] if kind == "planes4" else d)
+        self.diverged = False
+
+    def get(self, name):
+        return getattr(self, name).cpu().numpy()
+
+
+def _run_to(what, t_end, make):
+    """Integrate make() to a finite t_end or to its `diverged` stop (t_end is checked before
+    the sim is made: the refusal needs no device)."""
+    if not math.isfinite(t_end):
+        raise ValueError(f"{what}: a finite t_end")
+    return make().step(2**31 - 1, t_end)
+
+
 # ------------------------------------------------------------------ reinitialisation --
 # benchmarks/mac_reinit_test.py:23-113 (Rycroft 2018) through mac_reinit.hip: the reference map
 # is reset to the identity when the epoch's distortion gets large, the deformation gathered so
@@ -1018,7 +1114,7 @@ def epoch_distortion(J_ep, phi, out=None):
     return io.out(o)
 
 
-class MacReinitDisc:
+class MacReinitDisc(_LidDisc):
     """The loop body of benchmarks/mac_reinit_test.py:59-106 on device tensors, composed from
     operators (no fused step): a soft disc (R 0.2 at (0.6, 0.5)) in the lid cavity whose map
     is reinitialised when the epoch distortion max(max J, 1 / min J) over the solid exceeds
@@ -1030,39 +1126,24 @@ class MacReinitDisc:
     reinit=False: the plain loop, which folds and stops.  The advection skips the per-plane
     non-finite-velocity guard: the loop stops on a non-finite u before the next step reads it.
 
-    `record`: one (t, dist, min J_ep, max J_ep, n_reinit, max|u|) per step."""
+    `record`: one (t, dist, min J_ep, max J_ep, n_reinit, max|u|) per step.  state(): host
+    copies of u, v, X1, X2, Fs (4, N, N), phiref, and t, n_reinit."""
 
-    X0, Y0, R = 0.6, 0.5, 0.2
     STATE = ("u", "v", "X1", "X2", "Fs", "phiref", "t", "n_reinit")
+    KINDS = {**_LidDisc.KINDS, "Fs": "planes4", "n_reinit": int}
 
     def __init__(self, N=96, reinit=True, U_lid=1.0, mu_s=0.3, mu_f=0.01, rho=1.0, reinit_J=1.8):
-        import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("pyrmt_amd needs a visible MI355X")
-        self.torch, self.N, self.reinit, self.reinit_J = torch, int(N), bool(reinit), reinit_J
-        self.U_lid, self.mu_s, self.mu_f, self.rho = U_lid, mu_s, mu_f, rho
-        dx, dy = mac_grid(N, N)
-        self.dx, self.dy, self.w_t, self.nu = dx, dy, 2.0 * dx, mu_f / rho
-        xc = (np.arange(N) + 0.5) * dx
-        Xc, Yc = np.meshgrid(xc, xc)
-        Xg, Yg = np.meshgrid(np.arange(N) * dx, np.arange(N) * dy)
-        phi = np.sqrt((Xc - self.X0)**2 + (Yc - self.Y0)**2) - self.R          # :42-47
-        m = (phi <= 0).astype(float)
-        X1, X2 = extrapolate_reference_map(Xc * m, Yc * m, phi, dx, dy, 3)
-        dev = lambda h: torch.from_numpy(np.ascontiguousarray(h, dtype=np.float64)).cuda()
-        self.Xc, self.Yc, self.Xg, self.Yg = map(dev, (Xc, Yc, Xg, Yg))
-        self.X1, self.X2, self.phiref = dev(X1), dev(X2), dev(phi)
+        Xc, Yc, phi = self._setup(N, rho, mu_f)                                # :42-47
+        self.reinit, self.reinit_J = bool(reinit), reinit_J
+        self.U_lid, self.mu_s, self.mu_f = U_lid, mu_s, mu_f
+        dev = self._dev
+        self.Xc, self.Yc, self.phiref = dev(Xc), dev(Yc), dev(phi)
         one, zero = np.ones((N, N)), np.zeros((N, N))
         self.Fs = [dev(one), dev(zero), dev(zero), dev(one)]
-        self.u, self.v = dev(np.zeros((N, N + 1))), dev(np.zeros((N + 1, N)))
-        self.lx, self.ly = _axis_eigs(poisson_eigs_neumann(N, N, dx, dy))
-        cs = np.sqrt(mu_s / rho)
-        self.dt = float(min(0.3 * dx / U_lid, 0.2 * dx * dx / self.nu, 0.3 * dx / (cs + 1e-9)))
-        self.ctx = ctx_for(N, N)
-        self.stats = torch.empty(4, dtype=torch.float64, device="cuda")
-        self.t, self.nsteps, self.n_reinit, self.diverged, self.record = 0.0, 0, 0, False, []
+        self.dt = float(min(self._dt_bounds(self.dx, U_lid, self.nu, mu_s, rho)))
+        self.stats = self.torch.empty(4, dtype=self.torch.float64, device="cuda")
+        self.n_reinit, self.reinit_steps = 0, []
         self.phi = self.J_ep = None
-        self.reinit_steps = []
 
     def _geom(self):
         """:55-56: phi = phiref(xi), bilinear at the cell-centred offset."""
@@ -1073,8 +1154,8 @@ class MacReinitDisc:
 
     def _extrapolate_pairs(self, phi):
         dx, dy, Fs = self.dx, self.dy, self.Fs
-        Fs[0], Fs[1] = extrapolate_reference_map(Fs[0], Fs[1], phi, dx, dy, 3)
-        Fs[2], Fs[3] = extrapolate_reference_map(Fs[2], Fs[3], phi, dx, dy, 3)
+        Fs[0], Fs[1] = extrapolate_reference_map(Fs[0], Fs[1], phi, dx, dy, self.LAYERS)
+        Fs[2], Fs[3] = extrapolate_reference_map(Fs[2], Fs[3], phi, dx, dy, self.LAYERS)
 
     def step(self, nsteps=1, t_end=math.inf):
         from .functions import _advect_sl_rk4_multi
@@ -1091,19 +1172,15 @@ class MacReinitDisc:
             outs = [torch.empty_like(q) for q in qs]
             _advect_sl_rk4_multi(self.ctx, qs, u_c.contiguous(), v_c.contiguous(), self.Xg, self.Yg,
                                  dt, dx, dy, phi, outs)
-            self.X1, self.X2 = extrapolate_reference_map(outs[0], outs[1], phi, dx, dy, 3)
+            self.X1, self.X2 = extrapolate_reference_map(outs[0], outs[1], phi, dx, dy,
+                                                         self.LAYERS)
             self.Fs = outs[2:]
             self._extrapolate_pairs(phi)
             phi = self._geom()
             fu, fv, J_ep = total_force(self.X1, self.X2, self.Fs, phi, dx, dy, self.w_t, self.mu_s)
             ustar, vstar = momentum_predictor(u, v, self.nu, dx, dy, dt, self.U_lid, fu=fu, fv=fv,
                                               rho=self.rho)
-            # project(), the symbol's axes split once at set-up (not per step)
-            un, vn, p = torch.empty_like(u), torch.empty_like(v), torch.empty_like(phi)
-            L.check(L.lib().rmt_mac_project(self.ctx.bind(), _p(ustar), _p(vstar), dx, dy, dt,
-                                            float(self.rho), _hp(self.lx), _hp(self.ly), _p(un),
-                                            _p(vn), _p(p)), "project")
-            self.u, self.v = un, vn
+            self.u, self.v, _ = self._project(ustar, vstar, dt)
             self.t += dt
             self.nsteps += 1
             epoch_distortion(J_ep, phi, out=self.stats[:3])
@@ -1127,42 +1204,13 @@ class MacReinitDisc:
                 self.diverged = True
         return self
 
-    def state(self):
-        """Host copies of u, v, X1, X2, Fs (4, N, N), phiref, and t, n_reinit."""
-        g = lambda t: t.cpu().numpy()
-        return dict(u=g(self.u), v=g(self.v), X1=g(self.X1), X2=g(self.X2),
-                    Fs=np.stack([g(p) for p in self.Fs]), phiref=g(self.phiref), t=self.t,
-                    n_reinit=self.n_reinit)
-
-    def set_state(self, state):
-        """The fields of state() (arrays or device tensors; any subset)."""
-        unknown = set(state) - set(self.STATE)
-        if unknown:
-            raise KeyError(f"set_state: unknown fields {sorted(unknown)}; one of {self.STATE}")
-        N, io = self.N, _IO(None)
-        shapes = {"u": (N, N + 1), "v": (N + 1, N), "Fs": (4, N, N)}
-        for k, val in state.items():
-            if k in ("t", "n_reinit"):
-                setattr(self, k, float(val) if k == "t" else int(val))
-                continue
-            if tuple(np.shape(val)) != shapes.get(k, (N, N)):
-                raise ValueError(f"set_state: {k} has shape {tuple(np.shape(val))}")
-            d = io.dev(val).clone()
-            setattr(self, k, [d[i].contiguous() for i in range(4)] if k == "Fs" else d)
-        self.diverged = False
-
-    def get(self, name):
-        return getattr(self, name).cpu().numpy()
-
 
 def mac_reinit_run(N=96, t_end=15.0, reinit=True, U_lid=1.0, mu_s=0.3, mu_f=0.01, rho=1.0,
                    reinit_J=1.8, return_sim=False):
     """mac_reinit_test.py:36-113 (run): integrate to t_end or to the `diverged` stop; returns
     the time reached (return_sim: (t, the MacReinitDisc))."""
-    if not math.isfinite(t_end):
-        raise ValueError("mac_reinit_run: a finite t_end")
-    sim = MacReinitDisc(N, reinit, U_lid, mu_s, mu_f, rho, reinit_J)
-    sim.step(2**31 - 1, t_end)
+    sim = _run_to("mac_reinit_run", t_end,
+                  lambda: MacReinitDisc(N, reinit, U_lid, mu_s, mu_f, rho, reinit_J))
     return (sim.t, sim) if return_sim else sim.t
 
 
@@ -1270,7 +1318,7 @@ def advect_xi_conservative(xi, u, v, dx, dy, dt, phi, w_cut=0.0):
     return io.out(out)
 
 
-class MacSoftDisc:
+class MacSoftDisc(_LidDisc):
     """The loop body of benchmarks/mac_soft_disc_lid.py:79-150 on device tensors, composed from
     operators (no fused step): the soft disc (R 0.2 at (0.6, 0.5), kappa 0, rho 1, mu_f 0.01,
     w_t = 2 dx, U_lid 1, 3 extrapolation layers) under the integrator ladder.
@@ -1289,11 +1337,10 @@ class MacSoftDisc:
     non-finite velocity before the next step reads it.
 
     `record`: one (t, cx, cy, min J, max J) per step; `sl_steps`: the steps that took the
-    semi-Lagrangian branch; `pcg_iters`: the last step's two PCG counts."""
+    semi-Lagrangian branch; `pcg_iters`: the last step's two PCG counts.  state(): host copies
+    of u, v, X1, X2, and t."""
 
-    X0, Y0, R = 0.6, 0.5, 0.2
-    KAPPA, RHO, MU_F, U_LID, LAYERS = 0.0, 1.0, 0.01, 1.0, 3
-    STATE = ("u", "v", "X1", "X2", "t")
+    KAPPA, RHO, MU_F, U_LID = 0.0, 1.0, 0.01, 1.0
     SCHEMES = ("semilagrangian", "semilagrangian_cubic", "central2", "weno5")
 
     def __init__(self, N=128, integrator=None, imex=False, dt=None, mu_s=0.1,
@@ -1311,32 +1358,13 @@ class MacSoftDisc:
                              % (scheme, ", ".join(self.SCHEMES)))
         if scheme in ("central2", "weno5") and w_cut_fac == 0.0:
             w_cut_fac = 4.0                                                    # :43-45
-        import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("pyrmt_amd needs a visible MI355X")
-        from .bc import Disc
-        self.torch, self.N, self.scheme, self.mu_s = torch, int(N), scheme, float(mu_s)
+        self._setup(N, self.RHO, self.MU_F)                                    # :51
+        self.scheme, self.mu_s = scheme, float(mu_s)
         self.w_cut_fac, self.detg_clamp, self.isochoric = w_cut_fac, detg_clamp, bool(isochoric)
-        dx, dy = mac_grid(N, N)
-        rho = self.RHO
-        self.dx, self.dy, self.w_t, self.nu = dx, dy, 2.0 * dx, self.MU_F / rho
-        self.disc = Disc(self.X0, self.Y0, self.R)
-        cs = np.sqrt(mu_s / rho)
+        cs = np.sqrt(mu_s / self.RHO)
         self.cs2 = float(cs * cs) if self.use_elastic else 0.0                 # :113
         self.dt = float(self.default_dt(N, name, mu_s) if dt is None else dt)
-        xc = (np.arange(N) + 0.5) * dx
-        Xc, Yc = np.meshgrid(xc, xc)
-        Xg, Yg = np.meshgrid(np.arange(N) * dx, np.arange(N) * dy)
-        phi = self.disc(Xc, Yc)
-        m = (phi <= 0).astype(float)
-        X1, X2 = extrapolate_reference_map(Xc * m, Yc * m, phi, dx, dy, self.LAYERS)   # :51
-        dev = lambda h: torch.from_numpy(np.ascontiguousarray(h, dtype=np.float64)).cuda()
-        self.Xg, self.Yg, self.X1, self.X2 = map(dev, (Xg, Yg, X1, X2))
-        self.u, self.v = dev(np.zeros((N, N + 1))), dev(np.zeros((N + 1, N)))
-        self.lx, self.ly = _axis_eigs(poisson_eigs_neumann(N, N, dx, dy))
-        self.ctx = ctx_for(N, N)
-        self.stats = torch.empty(8, dtype=torch.float64, device="cuda")
-        self.t, self.nsteps, self.diverged, self.record = 0.0, 0, False, []
+        self.stats = self.torch.empty(8, dtype=self.torch.float64, device="cuda")
         self.sl_steps, self.pcg_iters = 0, (0, 0)
         self.phi = self.J = None
 
@@ -1359,9 +1387,8 @@ class MacSoftDisc:
         dx = 1.0 / N
         sl = integrator.endswith("-sl")
         _, use_imex, use_elastic = resolve_integrator(integrator[:-3] if sl else integrator)
-        cs = np.sqrt(mu_s / cls.RHO)
-        dt_adv = 0.3 * dx / cls.U_LID; dt_visc = 0.2 * dx * dx / (cls.MU_F / cls.RHO)
-        dt_elastic = 0.3 * dx / (cs + 1e-9)
+        dt_adv, dt_visc, dt_elastic = cls._dt_bounds(dx, cls.U_LID, cls.MU_F / cls.RHO, mu_s,
+                                                     cls.RHO)
         if sl and use_elastic:
             return 2.0 * dt_adv
         if sl:
@@ -1395,7 +1422,7 @@ class MacSoftDisc:
 
     def step(self, nsteps=1, t_end=math.inf):
         from .functions import rebuild_phi_from_reference_map
-        torch, dx, dy, dt, rho = self.torch, self.dx, self.dy, self.dt, self.RHO
+        dx, dy, dt, rho = self.dx, self.dy, self.dt, self.RHO
         for _ in range(int(nsteps)):
             if self.diverged or not self.t < t_end:
                 break
@@ -1417,11 +1444,7 @@ class MacSoftDisc:
             else:
                 ustar, vstar = momentum_predictor(u, v, self.nu, dx, dy, dt, self.U_LID, fu=fu,
                                                   fv=fv, rho=rho)
-            # project(), the symbol's axes split once at set-up (not per step)
-            un, vn, p = torch.empty_like(u), torch.empty_like(v), torch.empty_like(phi)
-            L.check(L.lib().rmt_mac_project(self.ctx.bind(), _p(ustar), _p(vstar), dx, dy, dt,
-                                            float(rho), _hp(self.lx), _hp(self.ly), _p(un),
-                                            _p(vn), _p(p)), "project")
+            un, vn, _ = self._project(ustar, vstar, dt)
             if self.use_elastic:                                                   # :130-137
                 umc, vmc = midpoint_centres(u, v, un, vn)
                 self._advect_maps(umc, vmc, phi)
@@ -1438,30 +1461,6 @@ class MacSoftDisc:
             self.record.append((self.t, sx / count, sy / count, minJ, maxJ))
         return self
 
-    def state(self):
-        """Host copies of u, v, X1, X2, and t."""
-        g = lambda t: t.cpu().numpy()
-        return dict(u=g(self.u), v=g(self.v), X1=g(self.X1), X2=g(self.X2), t=self.t)
-
-    def set_state(self, state):
-        """The fields of state() (arrays or device tensors; any subset)."""
-        unknown = set(state) - set(self.STATE)
-        if unknown:
-            raise KeyError(f"set_state: unknown fields {sorted(unknown)}; one of {self.STATE}")
-        N, io = self.N, _IO(None)
-        shapes = {"u": (N, N + 1), "v": (N + 1, N)}
-        for k, val in state.items():
-            if k == "t":
-                self.t = float(val)
-                continue
-            if tuple(np.shape(val)) != shapes.get(k, (N, N)):
-                raise ValueError(f"set_state: {k} has shape {tuple(np.shape(val))}")
-            setattr(self, k, io.dev(val).clone())
-        self.diverged = False
-
-    def get(self, name):
-        return getattr(self, name).cpu().numpy()
-
 
 def mac_soft_disc_run(N=128, t_end=8.0, scheme="semilagrangian", w_cut_fac=0.0, detg_clamp=0.0,
                       reinit=False, isochoric=False, imex=False, dt=None, integrator=None,
@@ -1469,11 +1468,8 @@ def mac_soft_disc_run(N=128, t_end=8.0, scheme="semilagrangian", w_cut_fac=0.0, 
     """mac_soft_disc_lid.py:23-157 (run(..., write=False)): integrate to t_end or to the
     `diverged` stop; returns the (n, 5) trajectory (t, cx, cy, min J, max J) (return_sim:
     (trajectory, the MacSoftDisc))."""
-    if not math.isfinite(t_end):
-        raise ValueError("mac_soft_disc_run: a finite t_end")
-    sim = MacSoftDisc(N, integrator=integrator, imex=imex, dt=dt, mu_s=mu_s, scheme=scheme,
-                      w_cut_fac=w_cut_fac, detg_clamp=detg_clamp, isochoric=isochoric,
-                      reinit=reinit)
-    sim.step(2**31 - 1, t_end)
+    sim = _run_to("mac_soft_disc_run", t_end, lambda: MacSoftDisc(
+        N, integrator=integrator, imex=imex, dt=dt, mu_s=mu_s, scheme=scheme, w_cut_fac=w_cut_fac,
+        detg_clamp=detg_clamp, isochoric=isochoric, reinit=reinit))
     traj = np.array(sim.record)
     return (traj, sim) if return_sim else traj

@@ -6,6 +6,8 @@ tests hold the same bits without storing them), and a NumPy restatement of the f
 operators and of one loop step per rung (the expensive operators through the oracle)."""
 import numpy as np
 
+from mac_faces_np import faces_of_stress
+
 # ---------------------------------------------------------------- traces ----
 N = 32
 DX = 1.0 / N
@@ -125,15 +127,11 @@ def advect_xi_conservative(xi, u, v, dx, dy, dt, phi, w_cut=0.0):
 def solid_force(O, X1, X2, phi, dx, dy, w_t, mu_s, kappa=0.0, detg_clamp=0.0, isochoric=False):
     """mac_soft_disc_lid.py:103-110 on the operators of O (the oracle, or the reference's
     functions module): (fu, fv, J, the three blended stresses)."""
-    ny, nx = phi.shape
     sxx, sxy, syy, J = O.solid_cauchy_stress(X1, X2, dx, dy, mu_s, kappa, phi,
                                              detg_clamp=detg_clamp, isochoric=isochoric)
     H = O.smoothed_heaviside(phi, w_t)
     Sxx = (1 - H) * sxx; Sxy = (1 - H) * sxy; Syy = (1 - H) * syy
-    divx = O.grad_central_x_2nd(Sxx, dx) + O.grad_central_y_2nd(Sxy, dy)
-    divy = O.grad_central_x_2nd(Sxy, dx) + O.grad_central_y_2nd(Syy, dy)
-    fu = np.zeros((ny, nx + 1)); fu[:, 1:-1] = 0.5 * (divx[:, 1:] + divx[:, :-1])
-    fv = np.zeros((ny + 1, nx)); fv[1:-1, :] = 0.5 * (divy[1:, :] + divy[:-1, :])
+    fu, fv = faces_of_stress(O, Sxx, Sxy, Syy, dx, dy)
     return fu, fv, J, (Sxx, Sxy, Syy)
 
 

@@ -17,6 +17,7 @@ import pytest
 
 from conftest import golden
 import mac_reinit_np as NP
+from mac_faces_np import faces_of_stress
 
 pytestmark = pytest.mark.gpu
 
@@ -123,13 +124,7 @@ def test_total_force_equals_its_unfused_composition(gpu, M, ops, name):
     Fs = [dev(p) for p in Fs]
     fu, fv, J = M.total_force(X1, X2, Fs, phi, dx, dy, w_t, mu_s)
     Sxx, Sxy, Syy, J0 = M.total_stress(X1, X2, Fs, phi, dx, dy, w_t, mu_s)
-    divx = gpu.grad_central_x_2nd(Sxx, dx) + gpu.grad_central_y_2nd(Sxy, dy)
-    divy = gpu.grad_central_x_2nd(Sxy, dx) + gpu.grad_central_y_2nd(Syy, dy)
-    ny, nx = phi.shape
-    fu0 = torch.zeros((ny, nx + 1), dtype=torch.float64, device="cuda")
-    fv0 = torch.zeros((ny + 1, nx), dtype=torch.float64, device="cuda")
-    fu0[:, 1:-1] = 0.5 * (divx[:, 1:] + divx[:, :-1])
-    fv0[1:-1, :] = 0.5 * (divy[1:, :] + divy[:-1, :])
+    fu0, fv0 = faces_of_stress(gpu, Sxx, Sxy, Syy, dx, dy)
     np.testing.assert_array_equal(fu.cpu().numpy(), fu0.cpu().numpy())
     np.testing.assert_array_equal(fv.cpu().numpy(), fv0.cpu().numpy())
     np.testing.assert_array_equal(J.cpu().numpy(), J0.cpu().numpy())
@@ -254,3 +249,57 @@ def test_mac_reinit_run_returns_the_time_reached(M, trace):
     assert sim.nsteps >= 4 and t == sim.t and abs(t - 3.5 * dt) < 1e-15
     np.testing.assert_array_equal([r[0] for r in sim.record[:3]], trace["record"][:3, 0])
     assert M.mac_reinit_run(int(trace["N"]), 2 * dt, reinit=False) == trace["record"][1, 0]
+
+
+def test_state_round_trip_and_set_state_contract(M):
+    """state() -> a fresh sim -> set_state -> state() holds every bit, from a step after a
+    reinitialisation (Fs != I, phiref stored); set_state's refusals, its copy of what it is given,
+    and its clearing of the `diverged` stop."""
+    import torch
+    N = 32
+    sim = M.MacReinitDisc(N, reinit_J=1.02)
+    while sim.n_reinit == 0 and sim.nsteps < 30:
+        sim.step(1)
+    assert sim.n_reinit == 1 and not sim.diverged
+    sim.step(1)
+    s = sim.state()
+    assert tuple(s) == M.MacReinitDisc.STATE
+    fresh = M.MacReinitDisc(N, reinit_J=1.02)
+    s0 = fresh.state()
+    assert not np.array_equal(s["Fs"], s0["Fs"]) and not np.array_equal(s["phiref"], s0["phiref"])
+    fresh.set_state(s)
+    s1 = fresh.state()
+    for k in M.MacReinitDisc.STATE:
+        np.testing.assert_array_equal(s1[k], s[k], err_msg=k)
+    assert type(s1["n_reinit"]) is int and s1["n_reinit"] == 1 and type(s1["t"]) is float
+    # the state is all a step reads: both sims take the same next step
+    sim.step(1); fresh.step(1)
+    assert fresh.record[-1] == sim.record[-1]
+    for k, a in fresh.state().items():
+        np.testing.assert_array_equal(a, sim.state()[k], err_msg=k)
+    # refusals
+    with pytest.raises(KeyError, match="unknown fields"):
+        fresh.set_state({"w": s["u"]})
+    with pytest.raises(ValueError, match="u has shape"):
+        fresh.set_state({"u": s["u"][:, :-1]})
+    with pytest.raises(ValueError, match="Fs has shape"):
+        fresh.set_state({"Fs": s["Fs"][:3]})
+    # what it is given is copied, not kept
+    u_dev, Fs_dev = torch.from_numpy(s["u"]).cuda(), torch.from_numpy(s["Fs"]).cuda()
+    u_keep, Fs_keep = u_dev.clone(), Fs_dev.clone()
+    fresh.set_state({"u": u_dev, "Fs": Fs_dev})
+    assert fresh.u.data_ptr() != u_dev.data_ptr() and fresh.Fs[0].data_ptr() != Fs_dev.data_ptr()
+    fresh.step(1)
+    assert torch.equal(u_dev, u_keep) and torch.equal(Fs_dev, Fs_keep)
+    # a `diverged` stop (no solid cell left: a stored level set that is positive everywhere),
+    # cleared by set_state
+    fresh.set_state(dict(s, phiref=np.ones((N, N))))
+    fresh.step(3)
+    n = fresh.nsteps
+    assert fresh.diverged and fresh.record[-1][1] == np.inf
+    fresh.step(3)
+    assert fresh.nsteps == n
+    fresh.set_state(s)
+    assert not fresh.diverged
+    fresh.step(1)
+    assert fresh.nsteps == n + 1 and not fresh.diverged and fresh.t > s["t"]

@@ -18,6 +18,7 @@ import pytest
 
 from conftest import golden
 import mac_soft_disc_np as NP
+from mac_faces_np import faces_of_stress
 
 pytestmark = pytest.mark.gpu
 
@@ -117,13 +118,7 @@ def test_solid_force_equals_its_unfused_composition(gpu, M, ops, name, var):
                                                 detg_clamp=clamp, isochoric=iso)
     H = gpu.smoothed_heaviside(phi, w_t)
     Sxx = (1 - H) * sxx; Sxy = (1 - H) * sxy; Syy = (1 - H) * syy
-    divx = gpu.grad_central_x_2nd(Sxx, dx) + gpu.grad_central_y_2nd(Sxy, dy)
-    divy = gpu.grad_central_x_2nd(Sxy, dx) + gpu.grad_central_y_2nd(Syy, dy)
-    ny, nx = phi.shape
-    fu0 = torch.zeros((ny, nx + 1), dtype=torch.float64, device="cuda")
-    fv0 = torch.zeros((ny + 1, nx), dtype=torch.float64, device="cuda")
-    fu0[:, 1:-1] = 0.5 * (divx[:, 1:] + divx[:, :-1])
-    fv0[1:-1, :] = 0.5 * (divy[1:, :] + divy[:-1, :])
+    fu0, fv0 = faces_of_stress(gpu, Sxx, Sxy, Syy, dx, dy)
     np.testing.assert_array_equal(fu.cpu().numpy(), fu0.cpu().numpy())
     np.testing.assert_array_equal(fv.cpu().numpy(), fv0.cpu().numpy())
     np.testing.assert_array_equal(J.cpu().numpy(), J0.cpu().numpy())
@@ -293,6 +288,52 @@ def test_folded_map_stops_without_a_row(M, fx):
     sim.set_state({f: fx[f"elastic_before12_{f}"] for f in ("u", "v", "X1", "X2")})
     sim.step(1)
     assert not sim.diverged and len(sim.record) == 1
+
+
+def test_state_round_trip_and_set_state_contract(M):
+    """state() -> a fresh sim -> set_state -> state() holds every bit; set_state's refusals, its
+    copy of what it is given, and its clearing of the `diverged` stop."""
+    import torch
+    sim = _sim(M, "elastic")
+    sim.step(4)
+    s = sim.state()
+    assert tuple(s) == M.MacSoftDisc.STATE and not sim.diverged
+    fresh = _sim(M, "elastic")
+    assert not np.array_equal(s["X1"], fresh.state()["X1"]) and s["u"].any()
+    fresh.set_state(s)
+    s1 = fresh.state()
+    for k in M.MacSoftDisc.STATE:
+        np.testing.assert_array_equal(s1[k], s[k], err_msg=k)
+    assert type(s1["t"]) is float
+    # the state is all a step reads: both sims take the same next step
+    sim.step(1); fresh.step(1)
+    assert fresh.record[-1] == sim.record[-1]
+    for k, a in fresh.state().items():
+        np.testing.assert_array_equal(a, sim.state()[k], err_msg=k)
+    # refusals
+    with pytest.raises(KeyError, match="unknown fields"):
+        fresh.set_state({"phi": s["X1"]})
+    with pytest.raises(ValueError, match="u has shape"):
+        fresh.set_state({"u": s["u"][:, :-1]})
+    # what it is given is copied, not kept
+    u_dev = torch.from_numpy(s["u"]).cuda()
+    u_keep = u_dev.clone()
+    fresh.set_state({"u": u_dev})
+    assert fresh.u.data_ptr() != u_dev.data_ptr()
+    fresh.step(1)
+    assert torch.equal(u_dev, u_keep)
+    # a `diverged` stop (test_folded_map_stops_without_a_row's folded map), cleared by set_state
+    bad = {f: s[f].copy() for f in ("X1", "X2")}
+    for f in ("X1", "X2"):
+        bad[f][[14, 17]] = bad[f][[17, 14]]
+    fresh.set_state(dict(s, **bad))
+    n = fresh.nsteps
+    fresh.step(3)
+    assert fresh.diverged and fresh.nsteps == n and fresh.t == s["t"]
+    fresh.set_state(s)
+    assert not fresh.diverged
+    fresh.step(1)
+    assert fresh.nsteps == n + 1 and not fresh.diverged and fresh.t > s["t"]
 
 
 # ---------------------------------------------------------------- physics, N = 48 ----

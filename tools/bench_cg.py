@@ -4,7 +4,6 @@ such a file).  For an A/B of two builds run it once per library (RMT_LIB), alter
   helmholtz   N=1024: rmt_mac_helmholtz, DST-preconditioned, u and v faces
   varrho      N=1025: the variable-density projection at CG_MAXITER = 20
 """
-import json
 import os
 import sys
 
@@ -14,30 +13,18 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pyrmt_amd import _lib as L, functions as F, mac as M  # noqa: E402
 from pyrmt_amd.bc import FreeSlipBox  # noqa: E402
-
-OUT = os.environ.get("RMT_BENCH_OUT")
+import _bench  # noqa: E402
 
 
 def emit(**kw):
-    line = json.dumps(dict(kw, lib=os.path.basename(L.LIB_PATH)))
-    print(line, flush=True)
-    if OUT:
-        with open(OUT, "a") as f:
-            f.write(line + "\n")
+    _bench.emit(**kw, lib=os.path.basename(L.LIB_PATH))
 
 
 def timed(fn, reps):
     """Median and spread of the device-event ms of fn over reps, after 2 warm-ups (the solves
     read r.r back every iteration, so this is the wall time of the call as well)."""
-    for _ in range(2):
-        fn()
-    ms = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); fn(); e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return float(np.median(ms)), float(min(ms)), float(max(ms))
+    return _bench.timed(fn, reps, warm=2, stat=lambda ms: (_bench.median(ms), float(min(ms)),
+                                                           float(max(ms))))
 
 
 def bench_helmholtz(N=1024, reps=9):

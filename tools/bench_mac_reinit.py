@@ -6,44 +6,18 @@ Usage: python tools/bench_mac_reinit.py [multi] [force] [loop]
   force   N=2048: rmt_mac_total_force against its unfused composition
   loop    N=1024: MacReinitDisc ms / step and the share of its three extrapolations
 """
-import json
 import os
 import sys
 import time
 
-import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import pyrmt_amd  # noqa: E402
 from pyrmt_amd import _lib as L, functions as F, mac as M  # noqa: E402
-
-OUT = os.environ.get("RMT_BENCH_OUT")
-
-
-def emit(**kw):
-    line = json.dumps(kw)
-    print(line, flush=True)
-    if OUT:
-        with open(OUT, "a") as f:
-            f.write(line + "\n")
-
-
-def timed(fn, reps, other=None):
-    """Median device-event ms of fn (and of other, alternating) over reps, after 3 warm-ups."""
-    fns = [fn] + ([other] if other else [])
-    for _ in range(3):
-        for f in fns:
-            f()
-    torch.cuda.synchronize()
-    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-           for _ in range(reps)] for _ in fns]
-    for r in range(reps):
-        for k, f in enumerate(fns):
-            ev[k][r][0].record(); f(); ev[k][r][1].record()
-    torch.cuda.synchronize()
-    med = [float(np.median([a.elapsed_time(b) for a, b in e])) for e in ev]
-    return med if other else med[0]
+from _bench import emit, timed  # noqa: E402
+from mac_faces_np import faces_of_stress  # noqa: E402
 
 
 def state(N):
@@ -92,13 +66,7 @@ def bench_force(sim, reps=15):
 
     def unfused():
         Sxx, Sxy, Syy, J = M.total_stress(X1, X2, Fs, phi, dx, dx, sim.w_t, sim.mu_s)
-        divx = F.grad_central_x_2nd(Sxx, dx) + F.grad_central_y_2nd(Sxy, dx)
-        divy = F.grad_central_x_2nd(Sxy, dx) + F.grad_central_y_2nd(Syy, dx)
-        fu = torch.zeros((N, N + 1), dtype=torch.float64, device="cuda")
-        fv = torch.zeros((N + 1, N), dtype=torch.float64, device="cuda")
-        fu[:, 1:-1] = 0.5 * (divx[:, 1:] + divx[:, :-1])
-        fv[1:-1, :] = 0.5 * (divy[1:, :] + divy[:-1, :])
-        return fu, fv, J
+        return (*faces_of_stress(F, Sxx, Sxy, Syy, dx, dx), J)
 
     t_f, t_u = timed(fused, reps, unfused)
     r0, r1 = fused(), unfused()
