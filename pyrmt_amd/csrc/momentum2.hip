@@ -394,7 +394,8 @@ int rmt_two_solid_diag(rmt_ctx *ctx, const double *phi_a, const double *phi_b, c
         RMT_LAUNCHED();
         for (int k = 0; k < 3; ++k) RMT_TRY(reduce_sum(ctx, m + k * n, n, r + 3 * s + k));
     }
-    k_negate<<<grid1d(n, 256), 256, 0, ctx->stream>>>(Jmin, n, m);   // min J = -max(-J)
+    // min J = -max(-J), a NaN kept as Jmin.min() keeps it (two_disc_contact.py:104)
+    k_negate<<<grid1d(n, 256), 256, 0, ctx->stream>>>(Jmin, n, m);
     RMT_LAUNCHED();
     RMT_TRY(reduce_max(ctx, m, n, r + 6));
     double h[7];

@@ -94,13 +94,16 @@ int ensure_bytes(rmt_ctx *ctx, size_t bytes) {
 // Deterministic two-pass reductions: RED_BLOCKS fixed workgroups each fold a strided
 // slice in a fixed order, then one workgroup folds the partials in a fixed tree.
 
-// OP 0 sum, 1 / 2 max (NaN inputs are not on the path: guarded upstream), 3 NaN-propagating max
+// OP 0 sum, 1 fmax with a NaN operand kept (ndarray.max; the bits of fmax wherever no NaN
+// arrives, +-0 ties included), 2 fmax (NaN inputs are not on the path: guarded upstream),
+// 3 NaN-propagating max
 template <int OP>
 __device__ __forceinline__ double red_op(double x, double y) {
+    if (OP == 1) return y != y ? y : x != x ? x : fmax(x, y);
     return OP == 0 ? x + y : OP == 3 ? nanmax_pick(x, y) : fmax(x, y);
 }
 
-template <int OP>  // 0 sum, 1 max, 2 max(a*a+b*b), 3 the same, NaN-propagating
+template <int OP>  // 0 sum, 1 max (a NaN comes out), 2 max(a*a+b*b), 3 the same, NaN-propagating
 __global__ void __launch_bounds__(RED_T) k_reduce_p1(const double *__restrict__ a,
                                                      const double *__restrict__ b, long n,
                                                      double *__restrict__ part) {
@@ -138,7 +141,7 @@ static int reduce_impl(rmt_ctx *ctx, int op, const double *a, const double *b, l
         k_reduce_p2<1><<<1, RED_T, 0, ctx->stream>>>(ctx->red, out, scale);
     } else if (op == 2) {
         k_reduce_p1<2><<<RED_BLOCKS, RED_T, 0, ctx->stream>>>(a, b, n, ctx->red);
-        k_reduce_p2<1><<<1, RED_T, 0, ctx->stream>>>(ctx->red, out, scale);
+        k_reduce_p2<2><<<1, RED_T, 0, ctx->stream>>>(ctx->red, out, scale);
     } else {
         k_reduce_p1<3><<<RED_BLOCKS, RED_T, 0, ctx->stream>>>(a, b, n, ctx->red);
         k_reduce_p2<3><<<1, RED_T, 0, ctx->stream>>>(ctx->red, out, scale);
@@ -147,6 +150,7 @@ static int reduce_impl(rmt_ctx *ctx, int op, const double *a, const double *b, l
     return RMT_OK;
 }
 int reduce_sum(rmt_ctx *ctx, const double *x, long n, double *o) { return reduce_impl(ctx, 0, x, x, n, o, 1.0); }
+// ndarray.max: a NaN in x comes out
 int reduce_max(rmt_ctx *ctx, const double *x, long n, double *o) { return reduce_impl(ctx, 1, x, x, n, o, 1.0); }
 int reduce_maxsq2(rmt_ctx *ctx, const double *a, const double *b, long n, double *o) {
     return reduce_impl(ctx, 2, a, b, n, o, 1.0);
@@ -1094,7 +1098,8 @@ int rmt_compute_timestep(rmt_ctx *ctx, const double *a, const double *b, double 
                          double CFL, double dt_min_cap, double mu_s, double rho_s, double gamma,
                          double rho_f, double mu_f, double eta_s, double kappa, double *dt) {
     (void)dy;
-    RMT_TRY(reduce_maxsq2(ctx, a, b, N_CELLS, ctx->red + RED_BLOCKS));
+    // np.max keeps a NaN; Python's min (the fmin chain below) then drops that bound
+    RMT_TRY(reduce_maxsq2_nan(ctx, a, b, N_CELLS, ctx->red + RED_BLOCKS));
     double m2;
     RMT_TRY(read_scalar(ctx, ctx->red + RED_BLOCKS, &m2));
     // functions.py:165-192 on the host (scalars); max(sqrt(.)) == sqrt(max(.))

@@ -692,7 +692,7 @@ __device__ __forceinline__ BCSrc bc_source(int kind, double lid, int j, int i, i
 // ------------------------------------------------------------------- reductions --
 constexpr int RED_BLOCKS = 1024, RED_T = 256;   // ctx->red holds RED_BLOCKS + 64 doubles
 int reduce_sum(rmt_ctx *ctx, const double *x, long n, double *dev_out);     // device scalar
-int reduce_max(rmt_ctx *ctx, const double *x, long n, double *dev_out);
+int reduce_max(rmt_ctx *ctx, const double *x, long n, double *dev_out);   // a NaN comes out
 int reduce_maxsq2(rmt_ctx *ctx, const double *a, const double *b, long n, double *dev_out);
 // the same with NaN propagating (a non-finite velocity makes the bound NaN: no SL block skip)
 int reduce_maxsq2_nan(rmt_ctx *ctx, const double *a, const double *b, long n, double *dev_out);
