@@ -77,7 +77,8 @@ int rmt_ctx_set_profiling(rmt_ctx *ctx, int on);
 int rmt_ctx_kernel_ms(rmt_ctx *ctx, double *ms2);
 /* Per-context implementation switches (bit-identical alternatives of the schedule and the
  * kernels, for A/B measurements and the regression tests): each starts from its environment
- * variable at rmt_ctx_create.  Names: ext_events, ex_arena_bump, ex_profile, fix_all,
+ * variable, read at rmt_ctx_create and nowhere else -- a variable changed after the library
+ * was loaded is seen by the contexts created afterwards.  Names: ext_events, ex_arena_bump, ex_profile, fix_all,
  * dct_rocfft, transpose2, sim_hiprio, sim_sync, early_geometry, early_transpose, fused_fluid,
  * no_overlap, side_tail, par_overlap, fused_fixprep, merged_join, test_delay_side,
  * test_delay_main, chain_cols, chain_layer_groups, chain_waves (8 or 16 waves per chain
@@ -87,9 +88,24 @@ int rmt_ctx_kernel_ms(rmt_ctx *ctx, double *ms2);
  * predictor and the divergence in one kernel, same bits), dct_sym (read when the context's DCT
  * plan is made, at its first solve; it chooses another FFT of the same DCT-I, equal to
  * rounding, not bit for bit), and the test-only test_delay_geo / test_nowait_drop (a slab's
- * early geometry delayed; a dropped geometry not waited for).  Set them before creating a sim or slab on the context (sim_hiprio is read
- * at rmt_sim_create); a change ends a carried step state.
- * Unknown name: RMT_EINVAL. */
+ * early geometry delayed; a dropped geometry not waited for).
+ * Four select a path and not merely a schedule (a value outside the range: RMT_EINVAL):
+ *   extrap_mode (no variable) 0: geometry-first chain path, row-ticket sweep when its capacity
+ *     limits are exceeded; 1: sweep only; 2: the chain path's pre-passes, then the sweep forced;
+ *     3: mode 0, then the abort status is raised (exercises the callers' error paths).
+ *   extrap_parallel (0 / 1, RMT_EXTRAP_PARALLEL) every fit of functions.py:95-161 -- the same
+ *     targets, acceptance, weights and raster-order known sets -- evaluated as the weighted
+ *     least-squares plane in offsets from the target and the layer solved as one sparse
+ *     triangular system by segments (extrap_par.hip), instead of the exact raster-order chain.
+ *     Not bit-exact: each fit differs from the reference by the reference's own rounding of
+ *     Cramer's rule on absolute coordinates (~1e-7 at N = 4096, the size of 1-ulp weight
+ *     noise).  A sim or slab schedules its step for the value it finds.
+ *   momentum_mode (RMT_MOM_UNFUSED non-zero gives 2) 0: one LDS-tiled kernel per RK4 stage;
+ *     2: unfused per-cell passes.  Bit-identical results in both.
+ *   list_blocks (>= 1, RMT_LIST_BLOCKS) the most workgroups of a launch over a device-side
+ *     tile list; same bits at any value.
+ * Set them before creating a sim or slab on the context (sim_hiprio is read at
+ * rmt_sim_create); a change ends a carried step state.  Unknown name: RMT_EINVAL. */
 int rmt_ctx_set_option(rmt_ctx *ctx, const char *name, int value);
 int rmt_ctx_get_option(rmt_ctx *ctx, const char *name, int *value);
 
@@ -143,21 +159,8 @@ int rmt_selftest_divk(rmt_ctx *ctx, const double *x, long n, double d, double *q
 int rmt_extrapolate_reference_map(rmt_ctx *ctx, const double *X1, const double *X2,
                                   const double *phi, double dx, double dy, int max_layers,
                                   double *X1_out, double *X2_out);
-/* librmt diagnostics for the extrapolation (no reference counterpart).  mode 0 (default):
- * geometry-first chain path, row-ticket sweep when its capacity limits are exceeded;
- * 1: sweep only; 2: chain path's pre-passes, then the sweep forced; 3: mode 0, then the
- * abort status is raised (exercises the callers' error paths).  rmt_extrap_last_path
- * (blocks) reports what the last call on ctx ran: 0 chain, 1 sweep. */
-int rmt_extrap_set_mode(int mode);
-/* Parallel extrapolation (no reference counterpart; default off, or RMT_EXTRAP_PARALLEL=1):
- * every fit of functions.py:95-161 -- the same targets, acceptance, weights and raster-order
- * known sets -- evaluated as the weighted least-squares plane in offsets from the target and
- * the layer solved as one sparse triangular system by segments (extrap_par.hip), instead of
- * the exact raster-order chain.  Not bit-exact: each fit differs from the reference by the
- * reference's own rounding of Cramer's rule on absolute coordinates (~1e-7 at N = 4096,
- * the size of 1-ulp weight noise).  Process-wide; applies to the
- * extrapolations started after the call. */
-int rmt_extrap_set_parallel(int on);
+/* librmt diagnostic (no reference counterpart; blocks): what the last extrapolation on ctx
+ * ran (the context options extrap_mode, extrap_parallel): 0 chain, 1 sweep. */
 int rmt_extrap_last_path(rmt_ctx *ctx, int *path);
 
 /* functions.py:1366-1367 with benchmarks/common.py:55-57: phi = |xi - (x0,y0)| - R */
@@ -223,10 +226,6 @@ int rmt_mixture_density(rmt_ctx *ctx, const double *phi_a, const double *phi_b, 
                         double rho_s, double rho_f, double *rho);
 int rmt_two_solid_diag(rmt_ctx *ctx, const double *phi_a, const double *phi_b, const double *X,
                        const double *Y, const double *Jmin, double *out5);
-
-/* librmt diagnostic (no reference counterpart): 0 (default) one LDS-tiled kernel per RK4
- * stage, 2 unfused per-cell passes.  Bit-identical results in both; other modes: RMT_EINVAL. */
-int rmt_momentum_set_mode(int mode);
 
 /* ---- projection (functions.py:1005-1364) ------------------------------------------- */
 /* functions.py:1016-1071 _compute_divergence_rc, constant density: d_f = dt / mean(rho) */

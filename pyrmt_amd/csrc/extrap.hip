@@ -707,13 +707,6 @@ __global__ void __launch_bounds__(EXW * 64) k_ex_sweep(ExSweep A, long long *gpr
     }
 }
 
-static int g_ex_mode = 0;   // rmt_extrap_set_mode
-// bumped by every change of the extrapolation's configuration (rmt_extrap_set_mode,
-// rmt_extrap_set_parallel): state an rmt_sim carries across calls was prepared for the old one
-static unsigned long g_ex_cfg_gen = 0;
-unsigned long extrap_config_gen() { return g_ex_cfg_gen; }
-void extrap_config_changed() { ++g_ex_cfg_gen; }
-
 // byte workspace: both paths' bit planes, the chain path's tables and its record arena
 ExWs extrap_layout(void *base, int ny, int nx, int max_layers, size_t *bytes, bool px,
                    bool bump) {
@@ -809,10 +802,10 @@ int extrap_geometry(rmt_ctx *ctx, const double *X1, const double *X2, const doub
     const int W = (nx + 63) / 64;
     RMT_CHECK(max_layers > 0 && ny >= 3 && nx >= 3 && ny < (1 << 20) && nx < (1 << 30),
               RMT_EINVAL, "extrapolation grid size");
-    const int force = g_ex_mode;
+    const int force = ctx->opt.extrap_mode;
     const bool chain = force != 1 && extrap_chain_supported(ny, nx, max_layers);
     // the parallel mode replaces the chain (never the diagnostic sweep modes)
-    const bool par = chain && force == 0 && extrap_par_enabled();
+    const bool par = chain && force == 0 && ctx->opt.extrap_parallel;
     RMT_TRY(ensure_bytes(ctx, extrap_workspace(ny, nx, max_layers, par)));
     const ExWs ws = extrap_layout(ctx->bytes, ny, nx, max_layers, nullptr, par,
                                   ctx->opt.ex_arena_bump);
@@ -898,7 +891,7 @@ int extrap_finish(rmt_ctx *ctx, double dx, double dy, int max_layers, double *X1
     const bool par = ctx->ex_par;
     const ExWs ws = extrap_layout(ctx->bytes, ny, nx, max_layers, nullptr, par,
                                   ctx->opt.ex_arena_bump);
-    const int force = g_ex_mode;
+    const int force = ctx->opt.extrap_mode;
     if (ctx->ex_noop_skip) {   // (extrap_geometry: nothing to fit, the map is left as it is)
         ctx->ex_noop_skip = false;
         if (dev_status) RMT_HIP(hipMemsetAsync(dev_status, 0, 2 * sizeof(int), ctx->stream));
@@ -1030,13 +1023,6 @@ std::string rmt::extrap_abort_detail(int code) {
     m += kind < 10 ? kinds[kind] : "?";
     m += " part " + std::to_string(part) + ", fit ordinal " + std::to_string(id);
     return m;
-}
-
-extern "C" int rmt_extrap_set_mode(int mode) {
-    RMT_CHECK(mode >= 0 && mode <= 3, RMT_EINVAL, "extrapolation mode must be 0 .. 3");
-    if (rmt::g_ex_mode != mode) rmt::extrap_config_changed();
-    rmt::g_ex_mode = mode;
-    return RMT_OK;
 }
 
 namespace rmt {

@@ -1,5 +1,5 @@
 // extrap_par.hip -- functions.py:48-163 extrapolate_reference_map, parallel mode (opt-in:
-// rmt_extrap_set_parallel / RMT_EXTRAP_PARALLEL=1).  NOT bit-exact: see below.
+// the context option extrap_parallel / RMT_EXTRAP_PARALLEL=1).  NOT bit-exact: see below.
 //
 // The reference fits a layer's targets in raster order and marks each known at once, so a
 // fit reads the fits before it (a Gauss-Seidel chain ~3000 fits deep at N = 4096: the exact
@@ -41,16 +41,8 @@
 // same fits serially (the GPU agrees to rounding: tests/test_gpu_extrap_par.py).
 #include "extrap.hpp"
 #include "exp_glibc.h"
-#include <cstdlib>
 
 namespace rmt {
-
-static int g_par = -1;   // -1: from RMT_EXTRAP_PARALLEL
-
-bool extrap_par_enabled() {
-    if (g_par < 0) g_par = getenv("RMT_EXTRAP_PARALLEL") && atoi(getenv("RMT_EXTRAP_PARALLEL"));
-    return g_par > 0;
-}
 
 __device__ __forceinline__ double px_wsum(double v) {   // butterfly: every lane gets the sum
 #pragma unroll
@@ -613,9 +605,3 @@ int extrap_par_values(rmt_ctx *ctx, const ExWs &ws, double *X1o, double *X2o, in
 }
 
 }  // namespace rmt
-
-extern "C" int rmt_extrap_set_parallel(int on) {
-    if ((on ? 1 : 0) != (rmt::extrap_par_enabled() ? 1 : 0)) rmt::extrap_config_changed();
-    rmt::g_par = on ? 1 : 0;
-    return RMT_OK;
-}

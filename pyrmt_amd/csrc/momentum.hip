@@ -932,7 +932,7 @@ static int mom_stage(rmt_ctx *ctx, const rmt_momentum_params *P, int s, const do
         nullptr, u_new, v_new, ws, TL, TC, W.dtp, olo, ohi, W.k2u, W.k2v, fluid_rows, K
     if (tlist) {
         auto kl = sq ? k_mom_stage_list<true> : k_mom_stage_list<false>;
-        kl<<<list_grid(ntiles), MS_T, 0, ctx->stream>>>(MS_ARGS(tlist, tcount, ntiles));
+        kl<<<list_grid(ctx, ntiles), MS_T, 0, ctx->stream>>>(MS_ARGS(tlist, tcount, ntiles));
     } else if (es) {
         // the edge tiles on their own stream, beside the interior launch: stage s's interior
         // waits for stage s - 1's edge tiles, its edge tiles for stage s - 1's interior (and
@@ -955,12 +955,10 @@ static int mom_stage(rmt_ctx *ctx, const rmt_momentum_params *P, int s, const do
     return RMT_OK;
 }
 
-// 0: per-stage kernels (k_mom_stage), 2: unfused per-cell passes (single domain, the
-// reference's pass structure; the schedule-independence tests' second opinion).  (A
-// temporally blocked RK4 kernel and a row-streaming stage kernel were measured slower in
-// rounds 2-3 and removed.)  RMT_MOM_UNFUSED=1 selects mode 2.
-static int g_mom_mode = getenv("RMT_MOM_UNFUSED") && atoi(getenv("RMT_MOM_UNFUSED")) ? 2 : 0;
-int momentum_mode() { return g_mom_mode; }
+// ctx->opt.momentum_mode 0: per-stage kernels (k_mom_stage), 2: unfused per-cell passes (single
+// domain, the reference's pass structure; the schedule-independence tests' second opinion).
+// (A temporally blocked RK4 kernel and a row-streaming stage kernel were measured slower in
+// rounds 2-3 and removed.)
 
 // Final BC (functions.py:760) on the boundary cells of rows [jb, je) only: the bottom / top
 // rows when the window holds them, then the side columns.
@@ -1003,7 +1001,7 @@ int momentum_rk4(rmt_ctx *ctx, const rmt_momentum_params *P, const double *u, co
     // that never reach the window's outputs)
     unsigned char *fluid_rows = fluid_rows_buf(W, w0.lo, nx);   // row w0.lo first
     bool rows_ready = W.fluid_rows_ready;
-    if (W.fluid_bits && g_mom_mode != 2 && nx % 64 == 0 && MS_TX == 64) {
+    if (W.fluid_bits && ctx->opt.momentum_mode != 2 && nx % 64 == 0 && MS_TX == 64) {
         // the phi producer left per-tile bits (k_sim_sl_t): the row flags from them
         const long nw = (long)(w0.hi - w0.lo) * tiles_x;
         k_fluid_rows_bits<<<grid1d(nw, 256), 256, 0, ctx->stream>>>(W.fluid_bits, tiles_x, w0.lo,
@@ -1012,7 +1010,7 @@ int momentum_rk4(rmt_ctx *ctx, const rmt_momentum_params *P, const double *u, co
         rows_ready = true;
     }
     const bool pskip = W.prep_const && rows_ready && nx % 64 == 0 && MS_TX == 64 &&
-                       g_mom_mode != 2;
+                       ctx->opt.momentum_mode != 2;
     if (pskip) {
         const long nseg = (long)(wp.je - wp.jb) * (nx / 64);
         k_mom_prep_seg<<<(unsigned)((nseg + 4 * PS_SEGS - 1) / (4 * PS_SEGS)), 256, 0, ctx->stream>>>(
@@ -1022,8 +1020,8 @@ int momentum_rk4(rmt_ctx *ctx, const rmt_momentum_params *P, const double *u, co
     } else {
         k_mom_prep<<<grid1d((long)(wp.je - wp.jb) * nx, 256), 256, 0, ctx->stream>>>(
             X1, X2, phi, ny, nx, P->dx, P->dy, P->mu_s, P->kappa, w_cut, clamp, P->w_t, P->rho_s,
-            P->rho_f, sxx, sxy, syy, J, W.H, g_mom_mode == 2 ? W.rho : nullptr, W.solid, wp.jb,
-            wp.je);
+            P->rho_f, sxx, sxy, syy, J, W.H, ctx->opt.momentum_mode == 2 ? W.rho : nullptr, W.solid,
+            wp.jb, wp.je);
     }
     RMT_LAUNCHED();
     // visc = eta_s > 0 and any(solid): cells with no solid contribute nothing anyway, so
@@ -1033,7 +1031,7 @@ int momentum_rk4(rmt_ctx *ctx, const rmt_momentum_params *P, const double *u, co
     const double coef[4] = {0.0, 0.5 * P->dt, 0.5 * P->dt, P->dt}, dt6 = P->dt / 6.0;
     double *kbu[2] = {W.k1u, W.k2u}, *kbv[2] = {W.k1v, W.k2v};
     if (ctx->prof) RMT_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
-    const bool unfused = g_mom_mode == 2;
+    const bool unfused = ctx->opt.momentum_mode == 2;
     hipStream_t es = nullptr;   // the edge-tile stream (edge_stream), when on
     if (!unfused) {
         (void)w_cut;
@@ -1092,12 +1090,12 @@ int fixup_phi_prep(rmt_ctx *ctx, const rmt_momentum_params *P, const MomWork &W,
                    double *sxy, double *syy, double *J, const int *tiles, const int *count,
                    int max_tiles, const int *st_src, int *st_dst, hipEvent_t done) {
     const int ny = ctx->ny, nx = ctx->nx;
-    RMT_CHECK(nx % 64 == 0 && g_mom_mode != 2, RMT_EINVAL,
+    RMT_CHECK(nx % 64 == 0 && ctx->opt.momentum_mode != 2, RMT_EINVAL,
               "fixup_phi_prep: nx % 64 == 0 and the fused momentum modes only");
     const double w_cut = P->stress_band ? P->w_t : 0.0, clamp = P->stress_band ? P->detg_clamp : 0.0;
-    RMT_HIP(launch_done(ctx, k_phi_prep_tiles, dim3(list_grid(max_tiles)), dim3(MOM_TX * MOM_TY), 0,
-                        ctx->stream, done, X1n, X2n, x0, y0, R, nbits, ny, nx, P->dx, P->dy,
-                        P->mu_s, P->kappa, w_cut, clamp, P->w_t, X1, X2, phi, sxx, sxy, syy, J,
+    RMT_HIP(launch_done(ctx, k_phi_prep_tiles, dim3(list_grid(ctx, max_tiles)),
+                        dim3(MOM_TX * MOM_TY), 0, ctx->stream, done, X1n, X2n, x0, y0, R, nbits,
+                        ny, nx, P->dx, P->dy, P->mu_s, P->kappa, w_cut, clamp, P->w_t, X1, X2, phi, sxx, sxy, syy, J,
                         W.H, W.solid, tiles, count, nx / MOM_TX, 0, ny, W.prep_const, st_src,
                         st_dst));
     return RMT_OK;
@@ -1116,7 +1114,7 @@ int momentum_fixup(rmt_ctx *ctx, const rmt_momentum_params *P, const double *u, 
     const RowWin w0 = win ? *win : RowWin{0, ny, 0, ny};
     auto grow = [&](int m) { return std::pair<int, int>{std::max(w0.jb - m, 0), std::min(w0.je + m, ny)}; };
     if (!skip_prep) {
-        k_mom_prep_tiles<<<list_grid(max_tiles), 256, 0, ctx->stream>>>(
+        k_mom_prep_tiles<<<list_grid(ctx, max_tiles), 256, 0, ctx->stream>>>(
             X1, X2, phi, ny, nx, P->dx, P->dy, P->mu_s, P->kappa, w_cut, clamp, P->w_t, P->rho_s,
             P->rho_f, sxx, sxy, syy, J, W.H, nullptr, W.solid, tiles, count, tiles_x,
             grow(7).first, grow(7).second, nx % 64 == 0 ? W.prep_const : nullptr);
@@ -1136,12 +1134,6 @@ int momentum_fixup(rmt_ctx *ctx, const rmt_momentum_params *P, const double *u, 
 }  // namespace rmt
 
 using namespace rmt;
-
-extern "C" int rmt_momentum_set_mode(int mode) {
-    RMT_CHECK(mode == 0 || mode == 2, RMT_EINVAL, "momentum mode must be 0 or 2");
-    rmt::g_mom_mode = mode;
-    return RMT_OK;
-}
 
 extern "C" int rmt_momentum_step_rk4(rmt_ctx *ctx, const rmt_momentum_params *P, const double *u,
                                      const double *v, const double *p, const double *X1,

@@ -51,19 +51,36 @@ static const struct { const char *name, *env; int rmt_opts::*f; } kOpts[] = {
     {"sl_zero_flags", "RMT_SL_ZERO_FLAGS", &rmt_opts::sl_zero_flags},
     {"dct_sym", "RMT_DCT_SYM", &rmt_opts::dct_sym},
     {"macp_fused", "RMT_MACP_FUSED", &rmt_opts::macp_fused},
+    {"extrap_mode", nullptr, &rmt_opts::extrap_mode},
+    {"extrap_parallel", "RMT_EXTRAP_PARALLEL", &rmt_opts::extrap_parallel},
+    {"momentum_mode", nullptr, &rmt_opts::momentum_mode},   // RMT_MOM_UNFUSED (below)
+    {"list_blocks", "RMT_LIST_BLOCKS", &rmt_opts::list_blocks},
 };
-int g_list_blocks = getenv("RMT_LIST_BLOCKS") ? std::max(1, atoi(getenv("RMT_LIST_BLOCKS")))
-                                                : LIST_BLOCKS;
+// what rmt_ctx_set_option refuses for the options with a closed range (nullptr: admitted)
+static const char *opt_range_error(int rmt_opts::*f, int value) {
+    if (f == &rmt_opts::ch_waves && value != 8 && value != 16) return "chain_waves is 8 or 16";
+    if (f == &rmt_opts::extrap_mode && (value < 0 || value > 3))
+        return "extrapolation mode must be 0 .. 3";
+    if (f == &rmt_opts::extrap_parallel && value != 0 && value != 1)
+        return "extrap_parallel is 0 or 1";
+    if (f == &rmt_opts::momentum_mode && value != 0 && value != 2)
+        return "momentum mode must be 0 or 2";
+    if (f == &rmt_opts::list_blocks && value < 1) return "list_blocks is at least 1";
+    return nullptr;
+}
 static rmt_opts opts_from_env() {
     rmt_opts o;
     for (const auto &k : kOpts)
         if (k.env)
             if (const char *e = getenv(k.env)) o.*(k.f) = atoi(e);
     if (const char *e = getenv("RMT_EX_ARENA")) o.ex_arena_bump = !strcmp(e, "bump");
+    if (const char *e = getenv("RMT_MOM_UNFUSED")) o.momentum_mode = atoi(e) ? 2 : 0;
     o.test_delay_side = std::max(0, o.test_delay_side);
     o.test_delay_main = std::max(0, o.test_delay_main);
     o.test_delay_geo = std::max(0, o.test_delay_geo);
     if (o.ch_waves != 8 && o.ch_waves != 16) o.ch_waves = rmt_opts().ch_waves;
+    o.extrap_parallel = o.extrap_parallel != 0;
+    o.list_blocks = std::max(1, o.list_blocks);
     return o;
 }
 
@@ -810,8 +827,8 @@ int rmt_ctx_set_option(rmt_ctx *ctx, const char *name, int value) {
     RMT_CHECK(ctx && name, RMT_EINVAL, "null argument");
     for (const auto &k : kOpts)
         if (!strcmp(k.name, name)) {
-            RMT_CHECK(k.f != &rmt_opts::ch_waves || value == 8 || value == 16, RMT_EINVAL,
-                      "chain_waves is 8 or 16");
+            const char *bad = opt_range_error(k.f, value);
+            RMT_CHECK(!bad, RMT_EINVAL, bad);
             ctx->opt.*(k.f) = value;
             ctx->bytes_gen++;   // a carried step state was prepared under the old options
             return RMT_OK;
@@ -1133,7 +1150,7 @@ int projection_rows(rmt_ctx *ctx, const double *a_star, const double *b_star, do
     RMT_TRY(ensure_scratch(ctx, 2 * n * sizeof(double)));
     double *rhs = ctx->scratch, *pc = rhs + n;
     if (tiles)   // the rhs of the other cells of the marked rows is still in scratch
-        k_divergence_tiles<<<list_grid(max_tiles), 256, 0, ctx->stream>>>(
+        k_divergence_tiles<<<list_grid(ctx, max_tiles), 256, 0, ctx->stream>>>(
             a_star, b_star, p_prev, ctx->ny, ctx->nx, rc_div(dx, dy), rhs, rho, dt, dtp, tiles, tcount,
             (ctx->nx + MOM_TX - 1) / MOM_TX);
     else if (!rowmark)

@@ -19,12 +19,8 @@ namespace rmt {
 
 // Workgroups of a launch over a device-side tile list (count on the device): kernels loop
 // b = blockIdx.x, b + gridDim.x, ... < *count; a fix-up list is a few hundred tiles, and a
-// launch of max_tiles mostly-empty workgroups costs its dispatch.
+// launch of max_tiles mostly-empty workgroups costs its dispatch (list_grid, below).
 constexpr int LIST_BLOCKS = 1024;
-extern int g_list_blocks;   // RMT_LIST_BLOCKS (A/B of the list launches' grid; ops.hip)
-inline unsigned list_grid(long max_tiles) {
-    return (unsigned)std::max(1L, std::min<long>(max_tiles, g_list_blocks));
-}
 
 // NaN-propagating max (a NaN operand wins; fmax would drop it)
 __host__ __device__ __forceinline__ double nanmax(double a, double b) {
@@ -157,6 +153,14 @@ struct rmt_opts {
                               // predictor and the scaled divergence in one tiled kernel
                               // (k_macp_predict_div; 0: k_macp_predict, k_macp_div), same bits;
                               // 6 % faster at N = 4096, not at 1024
+    int extrap_mode = 0;      // (no variable) extrapolation path: 0 chain (sweep on a capacity
+                              // fallback), 1 sweep only, 2 chain pre-passes then the sweep forced,
+                              // 3 mode 0 then an abort is reported (error-path tests)
+    int extrap_parallel = 0;  // RMT_EXTRAP_PARALLEL: the parallel extrapolation (extrap_par.hip)
+                              // in place of the chain -- not bit-exact, see there
+    int momentum_mode = 0;    // RMT_MOM_UNFUSED=1 gives 2: 0 one kernel per RK4 stage, 2 unfused
+                              // per-cell passes (single domain; the reference's pass structure)
+    int list_blocks = rmt::LIST_BLOCKS;   // RMT_LIST_BLOCKS: most workgroups of a list launch (>= 1)
 };
 
 #define RMT_EDGE_PRIOS 2   // edge-tile streams kept, one per priority (momentum.hip edge_stream)
@@ -220,6 +224,10 @@ struct StreamScope {
 int ensure_scratch(rmt_ctx *ctx, size_t bytes);    // >= bytes of double scratch
 int ensure_bytes(rmt_ctx *ctx, size_t bytes);      // >= bytes of byte scratch
 inline unsigned grid1d(long n, int block) { return (unsigned)((n + block - 1) / block); }
+// workgroups of a launch over a device-side list of at most max_tiles tiles (LIST_BLOCKS)
+inline unsigned list_grid(const rmt_ctx *ctx, long max_tiles) {
+    return (unsigned)std::max(1L, std::min<long>(max_tiles, ctx->opt.list_blocks));
+}
 #define N_CELLS ((long)ctx->ny * ctx->nx)          // of the `ctx` in scope
 
 // A launch whose completion also completes `done` (hipExtLaunchKernel's stop event tracks the
@@ -814,7 +822,6 @@ int momentum_rk4(rmt_ctx *ctx, const rmt_momentum_params *P, const double *u, co
 // re-run prep + the 4 stages on the 64 x 16 tiles listed in tiles[0 .. *count) (device) after
 // a speculative momentum_rk4 whose inputs changed only inside them (sim.hip overlap)
 constexpr int MOM_TX = 64, MOM_TY = 16;
-int momentum_mode();   // rmt_momentum_set_mode / RMT_MOM_MODE
 // the context's edge-tile stream at ctx->stream's priority (nullptr: opt.edge_stream off or no
 // stream of the context's own)
 int edge_stream(rmt_ctx *ctx, hipStream_t *out);
@@ -925,13 +932,6 @@ int extrap_sweep(rmt_ctx *ctx, double dx, double dy, int max_layers, double *X1o
                  hipStream_t s);
 size_t extrap_workspace(int ny, int nx, int max_layers, bool px = false);   // ctx->bytes used
 void imex_destroy(rmt_ctx *ctx);   // imex.hip: the context's DST plans
-// the parallel extrapolation mode (extrap_par.hip; rmt_extrap_set_parallel or the environment
-// variable RMT_EXTRAP_PARALLEL=1): the fits solved as one sparse triangular system by
-// segments instead of the exact raster-order chain -- not bit-exact, see extrap_par.hip
-bool extrap_par_enabled();
-// generation of the extrapolation's configuration (mode, parallel switch): bumped on a change
-unsigned long extrap_config_gen();
-void extrap_config_changed();
 // the exact no-op test of extrapolate() (k_ex_none) on rows [jb, je) of a whole known plane:
 // ctl[EXC_ANY] (extrap.hpp; zeroed by the caller) set iff a first-layer target there fits
 int extrap_none_rows(rmt_ctx *ctx, const unsigned long long *kbits, int ny, int nx, double dx,

@@ -97,7 +97,7 @@ struct rmt_sim {
     // projection's max |u|^2 partials stay valid), and the next call starts from them unless
     // rmt_sim_invalidate or another user of the context's workspace came in between
     bool carry_on = false, carry_valid = false, m2_valid = false;
-    unsigned long carry_gen = 0, carry_cfg = 0;   // workspace / extrapolation config generations
+    unsigned long carry_gen = 0;   // ctx->bytes_gen (workspace, options) the carry was left under
     hipEvent_t pev[7] = {};
     double ms[8] = {};
     long calls[8] = {};
@@ -933,7 +933,8 @@ int rmt_sim_create(rmt_ctx *ctx, const rmt_sim_params *prm, rmt_sim **out) {
     // size the shared scratch once (WENO5: 3 planes, projection: 2) and the extrapolation's
     // byte workspace, so nothing is reallocated while kernels are queued
     RMT_TRY(ensure_scratch(ctx, 3 * n * sizeof(double)));
-    RMT_TRY(ensure_bytes(ctx, extrap_workspace(ny, nx, prm->layers, extrap_par_enabled())));
+    RMT_TRY(ensure_bytes(ctx, extrap_workspace(ny, nx, prm->layers,
+                                               ctx->opt.extrap_parallel != 0)));
     if (prm->shape == RMT_SHAPE_DISC && prm->scheme == RMT_SCHEME_SEMILAGRANGIAN &&
         prm->layers >= 1 && prm->layers <= 12) {
         // the speculative momentum stream at the lowest priority: the extrapolation's own
@@ -1072,7 +1073,7 @@ static StepSched step_sched(const rmt_sim *S, double t_end) {
     // the parallel extrapolation: its values pass (~0.5 ms at N=4096, mostly the
     // one-workgroup combine) runs beside the speculative momentum too (RMT_PAR_OVERLAP=0:
     // in order, the momentum after it)
-    K.par = extrap_par_enabled();
+    K.par = o.extrap_parallel != 0;
     // the extrapolation chain occupies one CU for milliseconds; everything it does not
     // feed runs beside it: the momentum of every cell, from the pre-extrapolation map, on
     // a second stream, re-run afterwards on the tiles within reach of a target
@@ -1084,7 +1085,7 @@ static StepSched step_sched(const rmt_sim *S, double t_end) {
     // default on where nx % 64 == 0), which also copies the extrapolation's status; with it
     // the fallback sweep runs on the second stream beside the chain (the fix-up joins that
     // stream before it reads the map or the status)
-    K.fixprep = K.overlap && o.fused_fixprep && disc && nx64 && momentum_mode() != 2 &&
+    K.fixprep = K.overlap && o.fused_fixprep && disc && nx64 && o.momentum_mode != 2 &&
                 P.layers > 0;
     // k_phi_rebuild writes the momentum's pure-fluid flags (RMT_FUSED_FLUID, default on)
     K.fl_ok = o.fused_fluid && disc && nx64 && MOM_TX == 64;
@@ -1440,7 +1441,7 @@ static int step_side_stream(rmt_sim *S, const StepSched &K, StepRun &R) {
     if (K.split_proj) {
         RMT_HIP(hipMemsetAsync(S->rowmark, 0, ny, s2));
         if (K.diag_seg) RMT_HIP(hipMemsetAsync(S->tmark, 0, S->max_tiles, s2));
-        k_mark_rows<<<list_grid(S->max_tiles), 64, 0, s2>>>(
+        k_mark_rows<<<list_grid(ctx, S->max_tiles), 64, 0, s2>>>(
             S->tiles, S->tcount, (nx + MOM_TX - 1) / MOM_TX, ny, S->rowmark,
             K.diag_seg ? S->tmark : nullptr);
         RMT_LAUNCHED();
@@ -1517,7 +1518,7 @@ static int step_fixup(rmt_sim *S, const StepSched &K, StepRun &R, bool more) {
                                S->max_tiles, extrap_status(ctx, P.layers), S->flag + 2,
                                geo_next ? S->e_kb : nullptr));
     } else {
-        k_phi_tiles<<<list_grid(S->max_tiles), 256, 0, st>>>(
+        k_phi_tiles<<<list_grid(ctx, S->max_tiles), 256, 0, st>>>(
             S->X1n, S->X2n, ny, nx, P.x0, P.y0, P.R, S->phi, nullptr, nullptr, S->tiles,
             S->tcount, (nx + MOM_TX - 1) / MOM_TX, R.nb);
         RMT_LAUNCHED();
@@ -1689,8 +1690,7 @@ int rmt_sim_step(rmt_sim *S, int nsteps, double t_end) {
     R.ring_flag = K.solid ? S->flag : nullptr;
     // a carried state (rmt_sim_set_carry): this call's first step uses the geometry, known
     // plane, prep planes and max |u|^2 partials the previous call's last step left
-    const bool carry = S->carry_on && S->carry_valid && S->carry_gen == ctx->bytes_gen &&
-                       S->carry_cfg == extrap_config_gen();
+    const bool carry = S->carry_on && S->carry_valid && S->carry_gen == ctx->bytes_gen;
     const bool m2_ok = carry && S->m2_valid;
     S->carry_valid = false;
     // the zero-tile flags describe maps this call wrote (the caller may change them between calls)
@@ -1734,7 +1734,6 @@ int rmt_sim_step(rmt_sim *S, int nsteps, double t_end) {
     S->carry_valid = S->carry_on && R.geo_ready;
     S->m2_valid = R.m2_last;
     S->carry_gen = ctx->bytes_gen;
-    S->carry_cfg = extrap_config_gen();
     return RMT_OK;
 }
 

@@ -525,7 +525,8 @@ int rmt_slab_create(rmt_ctx *ctx, const rmt_sim_params *prm, int G, int rank,
     if (mu_max > 1e-12 && rho_min > 1e-12)
         d = std::fmin(d, CFL * rho_min * std::pow(dx, 2.0) / (4.0 * mu_max));
     S->dt_const = std::fmin(d, prm->dt_cap);
-    RMT_TRY(ensure_bytes(ctx, extrap_workspace(S->NY, S->NX, prm->layers, extrap_par_enabled())));
+    const bool par = ctx->opt.extrap_parallel != 0;
+    RMT_TRY(ensure_bytes(ctx, extrap_workspace(S->NY, S->NX, prm->layers, par)));
     if (prm->layers >= 1 && prm->layers <= 12) {
         int least = 0, greatest = 0;
         RMT_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
@@ -538,7 +539,7 @@ int rmt_slab_create(rmt_ctx *ctx, const rmt_sim_params *prm, int G, int rank,
         RMT_HIP(hipEventCreateWithFlags(&S->e_bits, hipEventDisableTiming));
         RMT_HIP(hipEventCreateWithFlags(&S->e_geo, hipEventDisableTiming));
         RMT_HIP(hipMalloc(&S->bits_next, (size_t)S->NY * W * sizeof(u64)));
-        S->ws_len = extrap_workspace(S->NY, S->NX, prm->layers, extrap_par_enabled());
+        S->ws_len = extrap_workspace(S->NY, S->NX, prm->layers, par);
         RMT_HIP(hipMalloc(&S->ws, S->ws_len));
     }
     RMT_HIP(hipStreamSynchronize(ctx->stream));

@@ -323,12 +323,7 @@ class DistributedSim:
         self.params, self.cfl = P, cfl
         self.rsplits = even_splits(N, self.G, HALO)
         self.csplits = even_splits(N, self.G, 2)
-        if options:
-            self.ctx = F._Ctx(N, N, torch.cuda.current_device())
-            for k, v in options.items():
-                self.ctx.set_option(k, v)
-        else:
-            self.ctx = F.ctx_for(N, N)
+        self.ctx = F.ctx_with(N, N, options)
         self.slabs = [Slab(self.ctx, P, self.G, r, self.rsplits, self.csplits)
                       for r in comm.ranks]
         self.dt_const = self.slabs[0].dt_const

@@ -8,6 +8,7 @@ like a drop-in) or torch CUDA float64 tensors (no copies; results come back as t
 Device memory and streams come from torch (plumbing only); the kernels are librmt's.
 """
 import ctypes
+import weakref
 
 import numpy as np
 
@@ -15,6 +16,8 @@ from . import _lib as L
 from .bc import resolve_bc, resolve_shape, Disc
 
 _ctxs = {}
+_live = weakref.WeakSet()   # every _Ctx of the process
+_defaults = {}              # options set process-wide (_set_everywhere): name -> value
 
 
 def _torch():
@@ -34,6 +37,9 @@ class _Ctx:
         h = ctypes.c_void_p()
         L.check(L.lib().rmt_ctx_create(ny, nx, device, None, ctypes.byref(h)), "rmt_ctx_create")
         self.h = h
+        for name, value in _defaults.items():
+            self.set_option(name, value)
+        _live.add(self)
 
     def bind(self):
         torch = _torch()
@@ -65,6 +71,26 @@ def ctx_for(ny, nx):
     if key not in _ctxs:
         _ctxs[key] = _Ctx(int(ny), int(nx), dev)
     return _ctxs[key]
+
+
+def ctx_with(ny, nx, options=None):
+    """The cached context of the grid, or with options (name -> value, rmt_ctx_set_option) a
+    context of the caller's own with these implementation switches."""
+    if not options:
+        return ctx_for(ny, nx)
+    c = _Ctx(int(ny), int(nx), _torch().cuda.current_device())
+    for name, value in options.items():
+        c.set_option(name, value)
+    return c
+
+
+def _set_everywhere(name, value):
+    """A context option for everything this process runs from now on: set on every context
+    there is, and on those created later.  A value the library refuses raises here, from the
+    first context (or a 5 x 5 probe when there is none yet), and changes nothing."""
+    for c in list(_live) or [_Ctx(5, 5, _torch().cuda.current_device())]:
+        c.set_option(name, value)
+    _defaults[name] = value
 
 
 class _IO:
@@ -185,8 +211,8 @@ def extrapolate_reference_map(X1, X2, phi, dx, dy, max_layers):
 def extrapolation_mode(mode):
     """librmt diagnostic: 0 chain path (default, sweep on capacity fallback), 1 sweep only,
     2 chain pre-passes then the sweep forced, 3 mode 0 then an abort is reported (error-path
-    tests)."""
-    L.check(L.lib().rmt_extrap_set_mode(int(mode)), "rmt_extrap_set_mode")
+    tests).  Process-wide, like extrapolation_parallel."""
+    _set_everywhere("extrap_mode", int(mode))
 
 
 def extrapolation_parallel(on=True):
@@ -195,7 +221,7 @@ def extrapolation_parallel(on=True):
     fit evaluated in offsets from its target (not bit-exact: within the reference's own
     rounding noise).  Process-wide, for the extrapolations that start
     afterwards (a simulation created afterwards also schedules its step for it)."""
-    L.check(L.lib().rmt_extrap_set_parallel(int(bool(on))), "rmt_extrap_set_parallel")
+    _set_everywhere("extrap_parallel", int(bool(on)))
 
 
 def extrapolation_last_path(ny, nx):
@@ -469,8 +495,8 @@ def compute_contact_force(phi1, phi2, k_rep, w_c, dx, dy):
 
 def momentum_mode(mode):
     """librmt diagnostic: 0 one kernel per RK4 stage (default), 2 unfused per-cell passes
-    (bit-identical); any other mode raises."""
-    L.check(L.lib().rmt_momentum_set_mode(int(mode)), "rmt_momentum_set_mode")
+    (bit-identical); any other mode raises.  Process-wide, like extrapolation_parallel."""
+    _set_everywhere("momentum_mode", int(mode))
 
 
 def velocity_rhs_blended_optimized(u, v, p, sigma_sxx_s_elastic, sigma_sxy_s_elastic,

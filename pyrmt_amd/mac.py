@@ -28,7 +28,7 @@ import math
 import numpy as np
 
 from . import _lib as L
-from .functions import _IO, _p, _plane_ptrs, ctx_for, extrapolate_reference_map
+from .functions import _IO, _p, _plane_ptrs, ctx_for, ctx_with, extrapolate_reference_map
 from .simulation import _wrap_device
 
 
@@ -624,13 +624,7 @@ class MacPeriodic:
             raise RuntimeError("pyrmt_amd needs a visible MI355X")
         self.torch, self.shape = torch, (int(ny), int(nx))
         self.dx, self.dy, self.nu, self.dt, self.rho = dx, dy, nu, dt, rho
-        if options:
-            from .functions import _Ctx
-            self.ctx = _Ctx(self.shape[0], self.shape[1], torch.cuda.current_device())
-            for k, val in options.items():
-                self.ctx.set_option(k, val)
-        else:
-            self.ctx = ctx_for(*self.shape)
+        self.ctx = ctx_with(*self.shape, options)
         self.lx, self.ly = _axis_eigs_per(lap_eigs_periodic(nx, ny, dx, dy), False)
         self.u, self.v, self.p = (torch.zeros(self.shape, dtype=torch.float64, device="cuda")
                                   for _ in range(3))
@@ -786,14 +780,7 @@ class MacMultiDisc:
         if not 1 <= len(self.specs) <= 8:
             raise ValueError("1..8 discs")
         P, self.dt = mac_params(N, self.specs, U_lid, mu_s, mu_f, rho, eta, dt)
-        if options:
-            # a context of its own with these implementation switches (rmt_ctx_set_option)
-            from .functions import _Ctx
-            self.ctx = _Ctx(N, N, torch.cuda.current_device())
-            for k, v in options.items():
-                self.ctx.set_option(k, v)
-        else:
-            self.ctx = ctx_for(N, N)
+        self.ctx = ctx_with(N, N, options)
         h = ctypes.c_void_p()
         L.check(L.lib().rmt_mac_sim_create(self.ctx.bind(), ctypes.byref(P), ctypes.byref(h)),
                 "rmt_mac_sim_create")

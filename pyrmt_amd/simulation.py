@@ -38,13 +38,7 @@ class Simulation:
         self.xs = np.ascontiguousarray(self.X[0, :]); self.ys = np.ascontiguousarray(self.Y[:, 0])
         self.disc = disc
         w_t = 2.0 * self.dx if w_t is None else w_t
-        if options:
-            # a context of its own with these implementation switches (rmt_ctx_set_option)
-            self.ctx = F._Ctx(N, N, torch.cuda.current_device())
-            for k, v in options.items():
-                self.ctx.set_option(k, v)
-        else:
-            self.ctx = F.ctx_for(N, N)
+        self.ctx = F.ctx_with(N, N, options)
         P = L.rmt_sim_params()
         P.ny = P.nx = N; P.dx = self.dx; P.dy = self.dy
         P.xs = self.xs.ctypes.data; P.ys = self.ys.ctypes.data

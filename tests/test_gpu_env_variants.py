@@ -43,6 +43,9 @@ environment variables still set a new context's defaults.
                         behind it
   sl_zero_flags=0       the second stream's SL pass loads and stores every tile instead of
                         skipping the tiles its zero-tile flags prove +0.0
+  list_blocks=3 / 1     the launches over the fix-up list with 3 workgroups (with fix_all: all
+                        64 tiles of the grid, 21 or 22 trips each) and with 1 instead of one
+                        per tile: the list kernels' second and later trips
 
 Every variant above runs the diagnostics through k_diag_seg (its segment skip adds nothing to
 any lane's sums, so the skip pattern does not change the bits).  diag_seg=0 (k_diag_p1's
@@ -101,6 +104,7 @@ def _same(got, ref):
     {"edge_stream": 0, "sl_phi": 0, "test_delay_side": 300}, {"skip_marked_rows": 0},
     {"tail_stream": 0}, {"tail_stream": 1, "test_delay_side": 300}, {"diag_first": 1},
     {"fused_fixprep": 0, "diag_first": 1}, {"sl_zero_flags": 0},
+    {"list_blocks": 3, "fix_all": 1}, {"list_blocks": 1},
 ], ids=lambda e: ",".join(f"{k}={v}" for k, v in e.items()))
 def test_schedule_switch_is_bit_identical(default_run, opts):
     _same(_run(opts), default_run)
@@ -147,6 +151,34 @@ def test_option_names_and_errors(gpu):
         c.set_option("dct_desc", 0)   # retired: the n = 4096 plan is always 13, 9, 7, 5
 
 
+def test_process_wide_setters_reach_every_context(gpu):
+    """functions.momentum_mode / extrapolation_parallel set their option on the contexts that
+    exist and on those created later; set_option on one context leaves the others alone; a
+    value out of range raises and changes nothing.  No kernel is launched."""
+    from pyrmt_amd import functions as F
+    modes = lambda c: (c.get_option("momentum_mode"), c.get_option("extrap_parallel"))
+    before = F._Ctx(64, 64, 0)
+    try:
+        F.momentum_mode(2)
+        F.extrapolation_parallel(True)
+        after = F._Ctx(64, 64, 0)
+        assert modes(before) == (2, 1) and modes(after) == (2, 1)
+        with pytest.raises(ValueError, match="momentum mode must be 0 or 2"):
+            F.momentum_mode(1)
+        assert modes(before) == (2, 1) and modes(F._Ctx(64, 64, 0)) == (2, 1)
+    finally:
+        F.momentum_mode(0)
+        F.extrapolation_parallel(False)
+    assert modes(before) == (0, 0) and modes(after) == (0, 0)
+    before.set_option("momentum_mode", 2)
+    assert modes(before) == (2, 0) and modes(after) == (0, 0)
+    with pytest.raises(ValueError, match="extrapolation mode must be 0 .. 3"):
+        before.set_option("extrap_mode", 4)
+    with pytest.raises(ValueError, match="momentum mode must be 0 or 2"):
+        after.set_option("momentum_mode", 1)
+    assert before.get_option("extrap_mode") == 0 and modes(after) == (0, 0)
+
+
 CHILD = r"""
 import sys
 import numpy as np
@@ -154,20 +186,36 @@ sys.path.insert(0, sys.argv[1])
 from pyrmt_amd.simulation import soft_disc_in_lid_driven
 s = soft_disc_in_lid_driven(256)
 assert s.ctx.get_option("chain_layer_groups") == 1 and s.ctx.get_option("fix_all") == 1
+assert s.ctx.get_option("list_blocks") == 3
 s.step(12)
 np.savez(sys.argv[2], **{f: s.get(f) for f in %r})
 """ % (FIELDS,)
 
 
+CHILD_MODES = r"""
+import sys
+sys.path.insert(0, sys.argv[1])
+from pyrmt_amd.functions import _Ctx
+c = _Ctx(64, 64, 0)
+got = [c.get_option(k) for k in ("extrap_parallel", "momentum_mode", "extrap_mode")]
+assert got == [1, 2, 0], got
+"""
+
+
 def test_environment_sets_context_defaults(tmp_path, default_run):
     out = str(tmp_path / "env.npz")
-    env = dict(os.environ, RMT_CH_LAYERS="1", RMT_FIX_ALL="1")
+    env = dict(os.environ, RMT_CH_LAYERS="1", RMT_FIX_ALL="1", RMT_LIST_BLOCKS="3")
     r = subprocess.run([sys.executable, "-c", CHILD, ROOT, out], env=env, capture_output=True,
                        text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]
     got = np.load(out)
     for f in FIELDS:
         np.testing.assert_array_equal(got[f], default_run[f], err_msg=f)
+    # the two variables that are not an option's value as it stands; no launch
+    env = dict(os.environ, RMT_EXTRAP_PARALLEL="1", RMT_MOM_UNFUSED="1")
+    r = subprocess.run([sys.executable, "-c", CHILD_MODES, ROOT], env=env, capture_output=True,
+                       text=True, timeout=110)
+    assert r.returncode == 0, r.stderr[-2000:]
 
 
 def _split_run(options, edit):

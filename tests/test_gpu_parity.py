@@ -159,6 +159,26 @@ def test_extrapolation_vs_oracle(gpu, oracle, name, mode):
         assert path == 1
 
 
+def test_extrapolation_mode_is_per_context(gpu, oracle):
+    """Two contexts of one grid in one process, the sweep-only mode on one of them alone:
+    alternating calls each take their own context's path, and all give the oracle's bits."""
+    import ctypes
+    import torch
+    from pyrmt_amd import _lib as L, functions as F
+    X1, X2, phi, dx, dy, layers = _extrap_case("rect_l1")
+    r1, r2 = _extrap_ref(oracle, "rect_l1")
+    a, b = F._Ctx(*phi.shape, 0), F.ctx_for(*phi.shape)
+    a.set_option("extrap_mode", 1)
+    d1, d2, dphi = (torch.from_numpy(x).cuda() for x in (X1, X2, phi))
+    for c, want in ((a, 1), (b, 0), (a, 1)):
+        o1, o2, path = torch.empty_like(d1), torch.empty_like(d1), ctypes.c_int(-1)
+        L.check(L.lib().rmt_extrapolate_reference_map(c.bind(), F._p(d1), F._p(d2), F._p(dphi),
+                                                      dx, dy, layers, F._p(o1), F._p(o2)))
+        L.check(L.lib().rmt_extrap_last_path(c.bind(), ctypes.byref(path)))
+        assert path.value == want
+        assert (o1.cpu().numpy() == r1).all() and (o2.cpu().numpy() == r2).all()
+
+
 _EXTRAP_REF = {}
 
 

@@ -117,34 +117,33 @@ def test_carry_with_a_derived_view_written_later(gpu):
     _same(a, b)
 
 
-@pytest.mark.parametrize("toggle", ["parallel", "mode"])
+@pytest.mark.parametrize("toggle", ["parallel", "mode", "ctx"])
 def test_carry_dropped_on_extrapolation_mode_change(gpu, toggle):
-    """Switching the extrapolation's configuration between step() calls (the parallel mode,
-    rmt_extrap_set_parallel; the path mode, rmt_extrap_set_mode) ends the carried geometry:
-    the next step runs the new configuration from scratch, bit-identical to a run with the
-    carry off (the carried geometry was the old mode's)."""
+    """Switching the extrapolation's configuration between step() calls (the context options
+    extrap_parallel and extrap_mode, through the process-wide setters; "ctx": extrap_mode on
+    the simulation's own context, rmt_ctx_set_option) ends the carried geometry: the next step
+    runs the new configuration from scratch, bit-identical to a run with the carry off
+    (the carried geometry was the old mode's)."""
     from pyrmt_amd.simulation import soft_disc_in_lid_driven
     from pyrmt_amd import functions as F
-    def on():
-        if toggle == "parallel":
-            F.extrapolation_parallel(True)
-        else:
-            F.extrapolation_mode(1)
-    def off():
-        if toggle == "parallel":
-            F.extrapolation_parallel(False)
-        else:
-            F.extrapolation_mode(0)
     a, b = soft_disc_in_lid_driven(256), soft_disc_in_lid_driven(256)
+    def switch(s, v):
+        if toggle == "parallel":
+            F.extrapolation_parallel(bool(v))
+        elif toggle == "mode":
+            F.extrapolation_mode(v)
+        else:
+            s.ctx.set_option("extrap_mode", v)
     _carry_off(b)
     try:
         for s in (a, b):
-            off()
+            switch(s, 0)
             s.step(3)
-            on()
+            switch(s, 1)
             s.step(3)
-            off()
+            switch(s, 0)
             s.step(3)
     finally:
-        off()
+        for s in (a, b):
+            switch(s, 0)
     _same(a, b)
