@@ -699,6 +699,50 @@ int rmt_mac_advect_xi_conservative(rmt_ctx *ctx, const double *xi, const double 
                                    const double *v, double dx, double dy, double dt,
                                    const double *phi, double w_cut, double *out);
 
+/* ---- viscoelastic constitutive layer (pyRMT/viscoelastic.py, viscoelastic.hip).  Elementwise
+ * over n >= 1 cells of equally long device planes, whatever the context's grid: a symmetric
+ * tensor is three planes (11, 12, 22), a velocity gradient L four (11, 12, 21, 22), each passed
+ * as a host array of device pointers.  An output plane may be its own input plane.  tau = inf
+ * gives 1 / tau = 0 exactly (:38, :107).  The arithmetic entries (ucm, stress) give the
+ * reference's bits; the others evaluate exp, log, sin, cos and atan2 exactly where the
+ * reference does and differ from it only through them. ---- */
+/* The elementwise launch of the entries below for n cells: workgroups and threads per
+ * workgroup; a thread walks k, k + blocks * threads, ... (host only, for the tests). */
+int rmt_ve_launch_shape(long n, int *blocks, int *threads);
+/* :27-42 ucm_local_rhs. */
+int rmt_ve_ucm_rhs(rmt_ctx *ctx, long n, const double *const *b, const double *const *L,
+                   double tau, double *const *out);
+/* :45-54 ucm_local_step applied nsteps >= 1 times, the state in registers between steps.
+ * track / out_err (both or neither): track is three host-array entries, each null or nsteps
+ * device doubles; out_err (n doubles) gets per cell the largest |component - track[step]| over
+ * the steps and the tracked components, as the running max(err, abs(..)) of
+ * benchmarks/viscoelastic_relaxation_test.py:32-36, :81 keeps it. */
+int rmt_ve_ucm_steps(rmt_ctx *ctx, long n, const double *const *b, const double *const *L,
+                     double tau, double dt, int nsteps, const double *const *track,
+                     double *const *out, double *out_err);
+/* :167-179 viscoelastic_stress: G b, plus G_inf bref where bref is given and G_inf != 0.0 (the
+ * branch of :175; not taken, the result is G * b with nothing added). */
+int rmt_ve_stress(rmt_ctx *ctx, long n, const double *const *b, double G,
+                  const double *const *bref, double G_inf, double *const *out);
+/* :71-76 sym_log and :79-84 sym_exp through _sym_eig2 (:63-68); np.maximum's NaN rule. */
+int rmt_ve_sym_log(rmt_ctx *ctx, long n, const double *const *a, double *const *out);
+int rmt_ve_sym_exp(rmt_ctx *ctx, long n, const double *const *a, double *const *out);
+/* :87-116 logconf_local_rhs (|lam2 - lam1| < 1e-10 selects exp(-l1), :104-106). */
+int rmt_ve_logconf_rhs(rmt_ctx *ctx, long n, const double *const *psi, const double *const *L,
+                       double tau, double *const *out);
+/* :133-147 relax_exact; tau = inf or dt == 0.0 copies the input bits (:140-141). */
+int rmt_ve_relax_exact(rmt_ctx *ctx, long n, const double *const *psi, double tau, double dt,
+                       double *const *out);
+/* :119-125 logconf_local_step (strang = 0) or :150-164 logconf_local_step_strang (strang = 1)
+ * applied nsteps >= 1 times in one launch: the bits of nsteps calls with nsteps = 1. */
+int rmt_ve_logconf_steps(rmt_ctx *ctx, long n, const double *const *psi, const double *const *L,
+                         double tau, double dt, int nsteps, int strang, double *const *out);
+/* benchmarks/mac_viscoelastic_uniform.py:30-32, :90-92: out3 (device, 3 doubles) = the largest
+ * eigenvalue of b over the cells with phi <= 0 (NaN propagates; -inf when there is none), the
+ * number of those cells, and b11 at the flat index `at`. */
+int rmt_ve_lam_max(rmt_ctx *ctx, long n, const double *const *b, const double *phi, long at,
+                   double *out3);
+
 /* The MAC step decomposed into row slabs (config 5 on several GPUs).
  * No reference interface: pyRMT runs mac_multi_disc_lid.py:62-98 in one process.  Slab
  * `rank` of G owns cell rows [row_splits[rank], row_splits[rank+1]) (even, > RMT_SLAB_HALO

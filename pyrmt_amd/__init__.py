@@ -16,6 +16,7 @@ from .functions import (_precompute_poisson_eigenvalues, _solve_poisson_dct,  # 
 from .output import output_simulation_data  # noqa: F401  (pyRMT/__init__.py:32)
 from . import simulation
 from . import mac
+from . import viscoelastic  # noqa: F401  (pyRMT/viscoelastic.py)
 
 __version__ = "0.1.0"
 

@@ -228,6 +228,17 @@ SIGNATURES = {
     "rmt_mac_midpoint_centres": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "rmt_mac_soft_diag": (_I, [_P, _P, _P, _P, _P, _D, _D, _P]),
     "rmt_mac_advect_xi_conservative": (_I, [_P, _P, _P, _P, _D, _D, _D, _P, _D, _P]),
+    # viscoelastic constitutive layer (viscoelastic.py, viscoelastic.hip)
+    "rmt_ve_launch_shape": (_I, [_L, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "rmt_ve_ucm_rhs": (_I, [_P, _L, _P, _P, _D, _P]),
+    "rmt_ve_ucm_steps": (_I, [_P, _L, _P, _P, _D, _D, _I, _P, _P, _P]),
+    "rmt_ve_stress": (_I, [_P, _L, _P, _D, _P, _D, _P]),
+    "rmt_ve_sym_log": (_I, [_P, _L, _P, _P]),
+    "rmt_ve_sym_exp": (_I, [_P, _L, _P, _P]),
+    "rmt_ve_logconf_rhs": (_I, [_P, _L, _P, _P, _D, _P]),
+    "rmt_ve_relax_exact": (_I, [_P, _L, _P, _D, _D, _P]),
+    "rmt_ve_logconf_steps": (_I, [_P, _L, _P, _P, _D, _D, _I, _I, _P]),
+    "rmt_ve_lam_max": (_I, [_P, _L, _P, _P, _L, _P]),
 }
 
 _lib = None
