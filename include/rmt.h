@@ -743,6 +743,51 @@ int rmt_ve_logconf_steps(rmt_ctx *ctx, long n, const double *const *psi, const d
 int rmt_ve_lam_max(rmt_ctx *ctx, long n, const double *const *b, const double *phi, long at,
                    double *out3);
 
+/* ---- the viscoelastic blob in the four-roll mill (benchmarks/mac_viscoelastic_extension.py,
+ * mac_ve.hip): what couples the constitutive layer above to the periodic staggered tier.  Planes
+ * are the context's (ny, nx) with ny, nx >= 3; face averages wrap, the gradients are the
+ * collocated utils.py:5-14 (one-sided at the first and last column / row).  Arithmetic entries
+ * give the reference's bits; H (sin), the exact lock (exp) and the FFT solves differ from it to
+ * rounding. ---- */
+/* :106, :119-120: u_c = 0.5 (u + roll(u, -1, 1)), v_c = 0.5 (v + roll(v, -1, 0)) and
+ * L = (d u_c / dx, d u_c / dy, d v_c / dx, d v_c / dy) in one launch.  Six output planes of
+ * their own. */
+int rmt_mac_ve_centre_kinematics(rmt_ctx *ctx, const double *u, const double *v, double dx,
+                                 double dy, double *u_c, double *v_c, double *const *L);
+/* :125-131: H = smoothed_heaviside(phi, w_t), S = (1 - H) G be, f_su / f_sv = div S averaged
+ * onto the x / y faces, Hu / Hv = H there, chi = 1 - H.  be: three planes (11, 12, 22).  Five
+ * output planes of their own. */
+int rmt_mac_ve_face_force(rmt_ctx *ctx, const double *const *be, const double *phi, double G,
+                          double w_t, double dx, double dy, double *f_su, double *f_sv, double *Hu,
+                          double *Hv, double *chi);
+/* mac.py:566-579: rhs = u - dt adv + dt f / rho + c_el (1 - chi_face) lap(u), both components
+ * (twodx = 2 dx, dx2 = dx^2, ... formed by the caller as the reference forms them). */
+int rmt_mac_per_imex_elastic_rhs(rmt_ctx *ctx, const double *u, const double *v, double twodx,
+                                 double twody, double dx2, double dy2, double dt, double c_el,
+                                 double rho, const double *chi, const double *fu,
+                                 const double *fv, double *rhs_u, double *rhs_v);
+/* mac.py:560-584 momentum_predictor_periodic_imex_elastic: that right-hand side, then
+ * (I - coef Lap) x = rhs per component (coef = dt nu + c_el; lx, ly: host, the per-axis
+ * symbol as for rmt_mac_per_solve).  Not in place. */
+int rmt_mac_per_predictor_imex_elastic(rmt_ctx *ctx, const double *u, const double *v,
+                                       double twodx, double twody, double dx2, double dy2,
+                                       double dt, double c_el, double coef, double rho,
+                                       const double *chi, const double *fu, const double *fv,
+                                       const double *lx, const double *ly, double *u_star,
+                                       double *v_star);
+/* :139-155 on one component of n faces.  mode 0 (explicit): star + dt (f_s + Hf beta
+ * (mill - u)) / rho; mode 1 (imex): mill + (star + dt f_s / rho - mill) exp(-dt beta Hf / rho);
+ * mode 2 (imex-elastic): the same without the force (u, f_s may be null where unused).  out
+ * may be star. */
+int rmt_mac_ve_lock(rmt_ctx *ctx, int mode, long n, const double *star, const double *u,
+                    const double *f_s, const double *Hf, const double *mill, double dt,
+                    double beta, double rho, double *out);
+/* :159-171 as one reduction over n cells: out5 (device, 5 doubles) = the largest eigenvalue
+ * of be over phi <= 0 (NaN propagates; -inf when there is none), the number of those cells,
+ * be11 at the flat index `at`, max |u| (NaN propagates) and 1.0 if u is all finite, else 0.0. */
+int rmt_mac_ve_record(rmt_ctx *ctx, long n, const double *const *be, const double *phi,
+                      const double *u, long at, double *out5);
+
 /* The MAC step decomposed into row slabs (config 5 on several GPUs).
  * No reference interface: pyRMT runs mac_multi_disc_lid.py:62-98 in one process.  Slab
  * `rank` of G owns cell rows [row_splits[rank], row_splits[rank+1]) (even, > RMT_SLAB_HALO

@@ -239,6 +239,15 @@ SIGNATURES = {
     "rmt_ve_relax_exact": (_I, [_P, _L, _P, _D, _D, _P]),
     "rmt_ve_logconf_steps": (_I, [_P, _L, _P, _P, _D, _D, _I, _I, _P]),
     "rmt_ve_lam_max": (_I, [_P, _L, _P, _P, _L, _P]),
+    # its coupling to the periodic MAC tier (mac.py MacViscoelasticExtension, mac_ve.hip)
+    "rmt_mac_ve_centre_kinematics": (_I, [_P, _P, _P, _D, _D, _P, _P, _P]),
+    "rmt_mac_ve_face_force": (_I, [_P, _P, _P, _D, _D, _D, _D, _P, _P, _P, _P, _P]),
+    "rmt_mac_per_imex_elastic_rhs": (_I, [_P, _P, _P, _D, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P,
+                                          _P]),
+    "rmt_mac_per_predictor_imex_elastic": (_I, [_P, _P, _P, _D, _D, _D, _D, _D, _D, _D, _D, _P,
+                                                _P, _P, _P, _P, _P, _P]),
+    "rmt_mac_ve_lock": (_I, [_P, _I, _L, _P, _P, _P, _P, _P, _D, _D, _D, _P]),
+    "rmt_mac_ve_record": (_I, [_P, _L, _P, _P, _P, _L, _P]),
 }
 
 _lib = None

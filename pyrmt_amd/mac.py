@@ -21,6 +21,10 @@ The soft disc under the integrator ladder (benchmarks/mac_soft_disc_lid.py, mac.
 698-721, mac_soft.hip): ``resolve_integrator``, ``solid_force``, ``midpoint_centres``,
 ``soft_diag``, ``advect_xi_conservative`` and the loop ``MacSoftDisc`` / ``mac_soft_disc_run``.
 Both loops stand on ``_LidDisc`` (the disc, the set-up, the projection, the state).
+The viscoelastic blob in the four-roll mill (benchmarks/mac_viscoelastic_extension.py,
+mac.py:560-584, mac_ve.hip): ``ve_centre_kinematics``, ``ve_face_force``,
+``momentum_predictor_periodic_imex_elastic``, ``ve_lock``, ``ve_record`` and the loop
+``MacViscoelasticExtension`` / ``mac_ve_extension_run`` / ``compare_integrators``.
 """
 import ctypes
 import math
@@ -339,8 +343,8 @@ def contact_stress(phi_a, phi_b, eta, Gsum, eps, dx, dy):
 # (centres) are all (Ny, Nx) planes and every index wraps.  The stencil operators are
 # bit-exact; the solves go through rocFFT on the half-spectrum (the reference: numpy.fft) and
 # the grid-wrap cubic splines of the semi-Lagrangian predictor through a windowed prefilter
-# (the reference: scipy.ndimage), both equal to rounding.  Not covered:
-# momentum_predictor_periodic_imex_elastic, advect_xi_conservative.
+# (the reference: scipy.ndimage), both equal to rounding.
+# momentum_predictor_periodic_imex_elastic stands with its driver at the end of this module.
 _small_ctxs = {}
 
 
@@ -1460,3 +1464,325 @@ def mac_soft_disc_run(N=128, t_end=8.0, scheme="semilagrangian", w_cut_fac=0.0, 
         detg_clamp=detg_clamp, isochoric=isochoric, reinit=reinit))
     traj = np.array(sim.record)
     return (traj, sim) if return_sim else traj
+
+
+# ------------------------------------------------- viscoelastic blob, four-roll mill ----
+# benchmarks/mac_viscoelastic_extension.py (a soft blob at the stagnation point of a four-roll
+# mill; the elastic limit diverges, the viscoelastic case saturates at b_xx = 1 / (1 - 2 Wi))
+# through mac_ve.hip: what joins the constitutive layer (pyrmt_amd.viscoelastic) to the periodic
+# tier above.  Planes are (Ny, Nx) with Ny, Nx >= 3; the face averages wrap, the gradients are
+# the collocated grad_central_*_2nd (one-sided at the first and last column / row).
+def _ve_shape(what, **planes):
+    """The common (Ny, Nx) of 2-D planes with Ny, Nx >= 3 (host check, before any device
+    call)."""
+    shapes = {k: tuple(np.shape(a)) for k, a in planes.items()}
+    first = next(iter(shapes.values()))
+    if len(first) != 2 or min(first) < 3 or any(sh != first for sh in shapes.values()):
+        raise ValueError(f"{what}: (Ny, Nx) planes of one shape with Ny, Nx >= 3; got {shapes}")
+    return first
+
+
+def ve_centre_kinematics(u, v, dx, dy):
+    """mac_viscoelastic_extension.py:106, :119-120 in one launch: (u_c, v_c, L11, L12, L21,
+    L22), u_c = 0.5 (u + roll(u, -1, 1)), v_c = 0.5 (v + roll(v, -1, 0)) and their
+    grad_central_{x,y}_2nd; the reference's bits."""
+    shape = _ve_shape("ve_centre_kinematics", u=u, v=v)
+    io = _IO(u, v); ud = io.dev(u); vd = io.dev(v)
+    o = io.empty((6,) + shape)
+    L.check(L.lib().rmt_mac_ve_centre_kinematics(_pctx(shape, True), _p(ud), _p(vd), float(dx),
+                                                 float(dy), _p(o[0]), _p(o[1]),
+                                                 _plane_ptrs([o[2], o[3], o[4], o[5]])),
+            "ve_centre_kinematics")
+    return tuple(io.out(o[k]) for k in range(6))
+
+
+def ve_face_force(be11, be12, be22, phi, G, w_t, dx, dy):
+    """mac_viscoelastic_extension.py:125-131: (f_su, f_sv, Hu, Hv, chi) of the stress
+    S = (1 - H) G b_e, H = smoothed_heaviside(phi, w_t): div S averaged onto the x / y faces, H
+    there, and chi = 1 - H at the centres."""
+    shape = _ve_shape("ve_face_force", be11=be11, be12=be12, be22=be22, phi=phi)
+    io = _IO(be11, be12, be22, phi)
+    b = [io.dev(a) for a in (be11, be12, be22)]; pd = io.dev(phi)
+    o = io.empty((5,) + shape)
+    L.check(L.lib().rmt_mac_ve_face_force(_pctx(shape, True), _plane_ptrs(b), _p(pd), float(G),
+                                          float(w_t), float(dx), float(dy),
+                                          *[_p(o[k]) for k in range(5)]), "ve_face_force")
+    return tuple(io.out(o[k]) for k in range(5))
+
+
+def _imex_elastic(what, solve, u, v, nu, dx, dy, dt, lap_eig, cs2, chi_c, fu, fv, rho):
+    shape = _ve_shape(what, u=u, v=v, chi_c=chi_c, fu=fu, fv=fv)
+    c_el = dt * dt * cs2                                                    # mac.py:573, 580
+    io = _IO(u, v, chi_c, fu, fv)
+    ud, vd, xd, fud, fvd = (io.dev(a) for a in (u, v, chi_c, fu, fv))
+    us = io.empty(shape); vs = io.empty(shape)
+    head = (_pctx(shape, True), _p(ud), _p(vd), float(2 * dx), float(2 * dy), float(dx**2),
+            float(dy**2), float(dt), float(c_el))
+    if solve:
+        if tuple(np.shape(lap_eig)) != shape:
+            raise ValueError(f"{what}: the fields and lap_eig differ in shape")
+        lx, ly = _axis_eigs_per(lap_eig, False)
+        L.check(L.lib().rmt_mac_per_predictor_imex_elastic(
+            *head, float(dt * nu + c_el), float(rho), _p(xd), _p(fud), _p(fvd), _hp(lx), _hp(ly),
+            _p(us), _p(vs)), what)
+    else:
+        L.check(L.lib().rmt_mac_per_imex_elastic_rhs(*head, float(rho), _p(xd), _p(fud), _p(fvd),
+                                                     _p(us), _p(vs)), what)
+    return io.out(us), io.out(vs)
+
+
+def momentum_predictor_periodic_imex_elastic(u, v, nu, dx, dy, dt, lap_eig, cs2, chi_c, fu, fv,
+                                             rho=1.0):
+    """mac.py:560-584: the IMEX predictor with the linearly-implicit elastic-wave stabiliser
+    c_el = dt^2 cs2: explicit central advection, the face force fu / fv inside the solve, the
+    defect c_el (1 - chi_face) lap that removes the stabiliser from the fluid, then
+    (I - (dt nu + c_el) Lap) x = rhs per component by FFT.  chi_c: the solid indicator at the
+    centres.  Returns (u*, v*)."""
+    return _imex_elastic("momentum_predictor_periodic_imex_elastic", True, u, v, nu, dx, dy, dt,
+                         lap_eig, cs2, chi_c, fu, fv, rho)
+
+
+def imex_elastic_rhs(u, v, dx, dy, dt, cs2, chi_c, fu, fv, rho=1.0):
+    """mac.py:566-579 alone: (rhs_u, rhs_v) of momentum_predictor_periodic_imex_elastic's two
+    solves (arithmetic only: the reference's bits)."""
+    return _imex_elastic("imex_elastic_rhs", False, u, v, 0.0, dx, dy, dt, None, cs2, chi_c, fu,
+                         fv, rho)
+
+
+VE_LOCK_MODES = {"explicit": 0, "imex": 1, "imex-elastic": 2}
+
+
+def ve_lock(star, u, f_s, Hf, mill, dt, beta, rho, mode):
+    """mac_viscoelastic_extension.py:139-155 on one velocity component: the solid force and the
+    lock of the fluid to the mill applied to the predictor's u* (`star`).  mode "explicit":
+    u* + dt (f_s + Hf beta (mill - u)) / rho; "imex": mill + (u* + dt f_s / rho - mill)
+    exp(-dt beta Hf / rho), the relaxation towards the mill integrated exactly; "imex-elastic":
+    the same without the force (it went into the predictor's solve)."""
+    if mode not in VE_LOCK_MODES:
+        raise ValueError(f"ve_lock: mode is one of {tuple(VE_LOCK_MODES)}, got {mode!r}")
+    shape = _ve_shape("ve_lock", star=star, u=u, f_s=f_s, Hf=Hf, mill=mill)
+    io = _IO(star, u, f_s, Hf, mill)
+    sd, ud, fd, hd, md = (io.dev(a) for a in (star, u, f_s, Hf, mill))
+    out = io.empty(shape)
+    L.check(L.lib().rmt_mac_ve_lock(_pctx(shape, True), VE_LOCK_MODES[mode], sd.numel(), _p(sd),
+                                    _p(ud), _p(fd), _p(hd), _p(md), float(dt), float(beta),
+                                    float(rho), _p(out)), "ve_lock")
+    return io.out(out)
+
+
+def ve_record(be11, be12, be22, phi, u, at, out=None):
+    """mac_viscoelastic_extension.py:159-171 as one reduction: five doubles, the largest
+    eigenvalue of b_e over phi <= 0 (NaN propagates; -inf without such a cell), the number of
+    those cells, be11 at the flat index `at`, max |u| (NaN propagates) and 1.0 / 0.0 for u all
+    finite or not (a device tensor for device inputs, written into `out` when given).  The
+    planes share one shape, of any rank."""
+    shapes = {tuple(np.shape(a)) for a in (be11, be12, be22, phi, u)}
+    if len(shapes) != 1 or not int(np.prod(next(iter(shapes)), dtype=np.int64)) >= 1:
+        raise ValueError(f"ve_record: non-empty planes of one shape, got {sorted(shapes)}")
+    io = _IO(be11, be12, be22, phi, u)
+    b = [io.dev(a) for a in (be11, be12, be22)]; pd = io.dev(phi); ud = io.dev(u)
+    o = io.empty((5,)) if out is None else out
+    L.check(L.lib().rmt_mac_ve_record(ctx_for(5, 5).bind(), pd.numel(), _plane_ptrs(b), _p(pd),
+                                      _p(ud), int(at), _p(o)), "ve_record")
+    return io.out(o)
+
+
+class MacViscoelasticExtension:
+    """The loop body of benchmarks/mac_viscoelastic_extension.py:102-171 on device tensors: a
+    soft blob (radius R at the centre of the unit square) in the four-roll mill
+    u_mill = U0 (sin kx cos ky, -cos kx sin ky), k = 2 pi, U0 = eps_rate / k, to which a
+    penalisation (beta = 150) locks the fluid.  A step: centre kinematics; phi rebuilt from the
+    map; the five planes X1, X2, p11, p12, p22 advected on one backtrace and masked; three
+    extrapolations (p22 with a zero partner); the log-conformation step (Strang under "imex" and
+    "imex-elastic", explicit RK2 otherwise); sym_exp; the face force; the integrator's predictor
+    (explicit, IMEX, elastic IMEX); the lock; the periodic projection; the record reduction,
+    whose five doubles are the step's one host read.  tau <= 0 means inf.  dt: the reference's
+    choice (:75-85) unless given.  t and dt are host floats formed as the reference forms them.
+
+    `record`: one (t, lam_max, b_xx(centre), max|u|) per step (lam_max NaN without a solid
+    cell); `dts`: the step sizes; history(t_end): the reference's view, every 100th step and
+    those with t >= t_end.  The loop stops (`stopped`, `clause`) when u is not all finite, no
+    solid cell is left or lam_max > 1e4 (:170)."""
+
+    LAYERS, BETA = 3, 150.0
+
+    def __init__(self, N=128, tau=0.5, eps_rate=0.5, G=0.3, mu_f=0.05, rho=1.0, R=0.13,
+                 integrator=None, imex=False, elastic_imex=False, dt=None):
+        from .functions import _torch
+        self.integrator, self.imex, self.elastic = resolve_integrator(
+            integrator, imex=imex, elastic_imex=elastic_imex, supports_elastic=True)
+        if int(N) != N or N < 3:
+            raise ValueError(f"MacViscoelasticExtension: N is a whole number >= 3, got {N!r}")
+        torch = _torch()
+        self.torch, self.N, self.R, self.G, self.rho = torch, int(N), float(R), G, rho
+        N = self.N
+        dx, dy = mac_grid(N, N)
+        self.dx, self.dy = dx, dy
+        xc = (np.arange(N) + 0.5) * dx; xf = np.arange(N) * dx                       # :52-60
+        Xc, Yc = np.meshgrid(xc, xc)
+        Xu, Yu = np.meshgrid(xf, xc); Xv, Yv = np.meshgrid(xc, xf)
+        Xg, Yg = np.meshgrid(xf, xf)
+        self.w_t = 2.0 * dx; self.nu = mu_f / rho
+        k = 2.0 * np.pi; U0 = eps_rate / k
+        u_mill = U0 * np.sin(k * Xu) * np.cos(k * Yu)
+        v_mill = -U0 * np.cos(k * Xv) * np.sin(k * Yv)
+        phi = np.sqrt((Xc - 0.5)**2 + (Yc - 0.5)**2) - R; m = (phi <= 0).astype(float)   # :64-66
+        X1, X2 = extrapolate_reference_map(Xc * m, Yc * m, phi, dx, dy, self.LAYERS)
+        dev = lambda h: torch.from_numpy(np.ascontiguousarray(h, dtype=np.float64)).cuda()
+        self.Xg, self.Yg, self.u_mill, self.v_mill, self.X1, self.X2 = map(
+            dev, (Xg, Yg, u_mill, v_mill, X1, X2))
+        z = lambda *s: torch.zeros(s + (N, N), dtype=torch.float64, device="cuda")
+        self.psi = [z() for _ in range(3)]
+        self.u, self.v, self.p, self.zero = z(), z(), z(), z()
+        cs = np.sqrt(G / rho)                                                        # :75-85
+        dt_adv = 0.25 * dx / max(U0, 0.1)
+        dt_visc = 0.2 * dx * dx / self.nu
+        dt_elastic = 0.3 * dx / (cs + 1e-9)
+        if dt is None:
+            dt = dt_adv if self.elastic else (min(dt_adv, dt_elastic) if self.imex
+                                              else min(dt_adv, dt_visc, dt_elastic))
+        self.dt = float(dt)
+        self.tau = math.inf if tau <= 0 else float(tau)                              # :86-90
+        self.Wi = eps_rate * self.tau
+        self.bxx_analytic = (math.inf if (self.tau == math.inf or self.Wi >= 0.5)
+                             else 1.0 / (1.0 - 2.0 * self.Wi))
+        self.lx, self.ly = _axis_eigs_per(lap_eigs_periodic(N, N, dx, dy), False)
+        self.ctx = ctx_for(N, N) if N >= 5 else None
+        self.kin, self.be, self.ff = z(6), z(3), z(5)
+        self.star = z(2)
+        self.stats = torch.empty(5, dtype=torch.float64, device="cuda")
+        self.phi = None
+        self.t, self.nsteps, self.stopped, self.clause = 0.0, 0, False, None
+        self.record, self.dts = [], []
+
+    def _bind(self):
+        return self.ctx.bind() if self.ctx is not None else _pctx((self.N, self.N), True)
+
+    def step(self, nsteps=1, t_end=None):
+        from .functions import _advect_sl_rk4_multi
+        torch, lib, N, dx, dy, rho = self.torch, L.lib(), self.N, self.dx, self.dy, self.rho
+        if self.ctx is None:
+            raise ValueError("MacViscoelasticExtension.step: N >= 5 (advection, extrapolation)")
+        t_end = math.inf if t_end is None else t_end
+        dt, n, at = self.dt, N * N, (N // 2) * N + N // 2
+        kin, be, ff, star = self.kin, self.be, self.ff, self.star
+        Lp = _plane_ptrs([kin[2], kin[3], kin[4], kin[5]])
+        bp = _plane_ptrs([be[0], be[1], be[2]])
+        mode = VE_LOCK_MODES[self.integrator]
+        for _ in range(int(nsteps)):
+            if self.stopped or not self.t < t_end:
+                break
+            if self.t + dt > t_end:
+                dt = t_end - self.t                                                # :104-105
+            c = self.ctx.bind()
+            L.check(lib.rmt_mac_ve_centre_kinematics(c, _p(self.u), _p(self.v), dx, dy, _p(kin[0]),
+                                                     _p(kin[1]), Lp), "centre kinematics")
+            phi = torch.empty_like(self.X1)
+            L.check(lib.rmt_rebuild_phi_disc(c, _p(self.X1), _p(self.X2), 0.5, 0.5, self.R,
+                                             _p(phi)), "rebuild_phi")              # :107
+            qs = [self.X1, self.X2] + self.psi
+            outs = [torch.empty_like(q) for q in qs]
+            _advect_sl_rk4_multi(self.ctx, qs, kin[0], kin[1], self.Xg, self.Yg, dt, dx, dy, phi,
+                                 outs)                                             # :110-116
+            self.X1, self.X2 = extrapolate_reference_map(outs[0], outs[1], phi, dx, dy,
+                                                         self.LAYERS)
+            p11, p12 = extrapolate_reference_map(outs[2], outs[3], phi, dx, dy, self.LAYERS)
+            p22, _ = extrapolate_reference_map(outs[4], self.zero, phi, dx, dy, self.LAYERS)
+            self.psi = [p11, p12, p22]
+            pp = _plane_ptrs(self.psi)
+            c = self.ctx.bind()
+            L.check(lib.rmt_ve_logconf_steps(c, n, pp, Lp, self.tau, dt, 1, int(self.imex), pp),
+                    "logconf step")                                                # :121-122
+            L.check(lib.rmt_ve_sym_exp(c, n, pp, bp), "sym_exp")
+            L.check(lib.rmt_mac_ve_face_force(c, bp, _p(phi), float(self.G), self.w_t, dx, dy,
+                                              *[_p(ff[k]) for k in range(5)]), "face force")
+            us, vs = star[0], star[1]
+            if self.elastic:                                                       # :137-138
+                c_el = dt * dt * (self.G / rho)
+                L.check(lib.rmt_mac_per_predictor_imex_elastic(
+                    c, _p(self.u), _p(self.v), float(2 * dx), float(2 * dy), float(dx**2),
+                    float(dy**2), dt, float(c_el), float(dt * self.nu + c_el), float(rho),
+                    _p(ff[4]), _p(ff[0]), _p(ff[1]), _hp(self.lx), _hp(self.ly), _p(us), _p(vs)),
+                    "elastic IMEX predictor")
+            elif self.imex:                                                        # :146
+                L.check(lib.rmt_mac_per_predictor_imex(
+                    c, _p(self.u), _p(self.v), float(2 * dx), float(2 * dy), dt,
+                    float(dt * self.nu), _hp(self.lx), _hp(self.ly), _p(us), _p(vs)),
+                    "IMEX predictor")
+            else:                                                                  # :154
+                L.check(lib.rmt_mac_per_predictor(
+                    c, _p(self.u), _p(self.v), float(self.nu), float(dx**2), float(dy**2),
+                    float(2 * dx), float(2 * dy), dt, _p(us), _p(vs)), "explicit predictor")
+            for s, w, f, H, mill in ((us, self.u, ff[0], ff[2], self.u_mill),
+                                     (vs, self.v, ff[1], ff[3], self.v_mill)):     # :139-155
+                L.check(lib.rmt_mac_ve_lock(c, mode, n, _p(s), _p(w), _p(f), _p(H), _p(mill), dt,
+                                            self.BETA, float(rho), _p(s)), "lock")
+            L.check(lib.rmt_mac_per_project(c, _p(us), _p(vs), dx, dy, float(rho / dt),
+                                            float(dt / rho), _hp(self.lx), _hp(self.ly),
+                                            _p(self.u), _p(self.v), _p(self.p)), "project")  # :156
+            L.check(lib.rmt_mac_ve_record(c, n, bp, _p(phi), _p(self.u), at, _p(self.stats)),
+                    "record")
+            self.t += dt
+            self.nsteps += 1
+            lam, count, bxx_c, umax, finite = self.stats.tolist()    # the step's one host read
+            if count == 0:
+                lam = math.nan                                                     # :160
+            self.phi = phi
+            self.record.append((self.t, lam, bxx_c, umax))
+            self.dts.append(dt)
+            if not finite or count == 0 or lam > 1e4:                              # :170
+                self.stopped = True
+                self.clause = ("non-finite u" if not finite else "no solid cell" if count == 0
+                               else "lam_max > 1e4")
+        return self
+
+    def history(self, t_end=math.inf):
+        """The reference's `hist` (:163-164): every 100th step and those with t >= t_end."""
+        return [r for k, r in enumerate(self.record, 1) if k % 100 == 0 or r[0] >= t_end]
+
+    def get(self, name):
+        """Host copy of u, v, p, X1, X2, phi, p11, p12, p22, be11, be12, be22, u_c, v_c, f_su,
+        f_sv, Hu, Hv or chi (the last step's)."""
+        planes = dict(u=self.u, v=self.v, p=self.p, X1=self.X1, X2=self.X2, phi=self.phi,
+                      p11=self.psi[0], p12=self.psi[1], p22=self.psi[2], be11=self.be[0],
+                      be12=self.be[1], be22=self.be[2], u_c=self.kin[0], v_c=self.kin[1],
+                      f_su=self.ff[0], f_sv=self.ff[1], Hu=self.ff[2], Hv=self.ff[3],
+                      chi=self.ff[4])
+        return planes[name].cpu().numpy()
+
+
+def mac_ve_extension_run(N=128, t_end=12.0, tau=0.5, eps_rate=0.5, G=0.3, mu_f=0.05, rho=1.0,
+                         R=0.13, imex=False, elastic_imex=False, dt=None, integrator=None,
+                         return_sim=False):
+    """mac_viscoelastic_extension.run (:41-189) without frames and files: integrate to t_end or
+    to the stop; returns (t, hist) as the reference does (return_sim: (t, hist, the
+    MacViscoelasticExtension))."""
+    if not math.isfinite(t_end):
+        raise ValueError("mac_ve_extension_run: a finite t_end")
+    sim = MacViscoelasticExtension(N, tau, eps_rate, G, mu_f, rho, R, integrator, imex,
+                                   elastic_imex, dt).step(2**31 - 1, t_end)
+    hist = sim.history(t_end)
+    return (sim.t, hist, sim) if return_sim else (sim.t, hist)
+
+
+def compare_integrators(N=40, tau=0.5, t_end=1.0, eps_rate=0.5, G=0.3, mu_f=0.05):
+    """mac_viscoelastic_extension.compare_integrators (:253-280) as data: explicit against IMEX
+    at the explicit viscous step (regression), and both at 2, 3 and 4 times it (capability).
+    Returns dict(dt_visc, dt_elastic, explicit_bxx, imex_bxx, rel, rows), rows one (factor,
+    explicit reached the end, IMEX reached the end, IMEX b_xx, its relative difference from
+    explicit_bxx) per factor."""
+    dx = 1.0 / N; nu = mu_f
+    dt_visc = 0.2 * dx * dx / nu
+    dt_elastic = 0.3 * dx / (np.sqrt(G) + 1e-9)
+    cfg = dict(N=N, tau=tau, t_end=t_end, eps_rate=eps_rate, G=G, mu_f=mu_f)
+    last = lambda h: h[-1][2] if h else math.nan
+    end = lambda h: bool(h) and h[-1][0] >= t_end - 1e-9
+    br = last(mac_ve_extension_run(imex=False, dt=dt_visc, **cfg)[1])
+    bs = last(mac_ve_extension_run(imex=True, dt=dt_visc, **cfg)[1])
+    rows = []
+    for fac in (2, 3, 4):
+        he = mac_ve_extension_run(imex=False, dt=fac * dt_visc, **cfg)[1]
+        hi = mac_ve_extension_run(imex=True, dt=fac * dt_visc, **cfg)[1]
+        rows.append((fac, end(he), end(hi), last(hi), abs(last(hi) - br) / br))
+    return dict(dt_visc=dt_visc, dt_elastic=dt_elastic, explicit_bxx=br, imex_bxx=bs,
+                rel=abs(bs - br) / br, rows=rows)

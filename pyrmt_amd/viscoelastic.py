@@ -14,8 +14,9 @@ back in the caller's array type; a call whose inputs are all scalars returns Pyt
 The steppers take `nsteps`: that many steps in one launch, the state in registers in between,
 with the bits of `nsteps` single calls.  ucm_* and viscoelastic_stress give the reference's
 bits; the others differ from it through exp, log, sin, cos and atan2 alone (DESIGN.md
-section 18).  The coupled drivers (elastic IMEX, mac_viscoelastic_disc / _extension) are not
-built."""
+section 18).  The coupled four-roll-mill driver (mac_viscoelastic_extension, elastic IMEX)
+stands on this layer in pyrmt_amd.mac (MacViscoelasticExtension); the lid
+cavity's mac_viscoelastic_disc is not built."""
 import ctypes
 import math
 
